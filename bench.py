@@ -14,17 +14,22 @@ Driver contract:
   RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the env.)
 Rank 0 prints ONE JSON line; timing is W untimed warmups then EXACTLY K
 steps bracketed by barrier + torch.cuda.synchronize on both sides, MAX over
-ranks.  --svm additionally reports the CoCoA-SVM samples/sec secondary
-metric in config.
+ranks.  A plain run does only that (setup, warmup, the K timed steps, the
+JSON line).  --full additionally runs the CoCoA-SVM secondary bench and
+reports its samples/sec in config.  --dump-outputs DIR writes the factors
+the last timed step produced as DIR/<name>.npy (float32) so two builds can
+be compared output for output.
 """
 
 from __future__ import annotations
 
 import argparse
 import json
+import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 from flink_ms_amd.data.libsvm import LibSVMShape, synthetic_libsvm
@@ -58,11 +63,19 @@ def parse_args(argv=None):
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--scale-1b", action="store_true",
                    help="1B-rating config: 125M ratings x 1.25M users per GPU")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements (the CoCoA-SVM "
+                        "bench); a plain run times only the ALS flagship")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the factors computed "
+                        "by the last timed step as DIR/<name>.npy (float32, "
+                        "at most 64 MB in all; larger outputs are reduced "
+                        "to a fixed seeded row sample)")
     p.add_argument("--svm", action="store_true",
                    help="deprecated no-op: the CoCoA-SVM secondary bench "
-                        "now runs by default")
+                        "runs under --full")
     p.add_argument("--no-svm", action="store_true",
-                   help="skip the CoCoA-SVM secondary bench")
+                   help="skip the CoCoA-SVM secondary bench under --full")
     p.add_argument("--svm-rows-per-gpu", type=int, default=697_641)
     p.add_argument("--overlap", choices=["auto", "off", "force"],
                    default="auto",
@@ -70,6 +83,30 @@ def parse_args(argv=None):
                         "the comm-stream pipeline even at world 1)")
     p.add_argument("--device", default=None, help="cpu override for tests")
     return p.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000   # all dumped arrays together
+DUMP_SAMPLE_SEED = 20240521
+
+
+def dump_outputs(outdir, arrays):
+    """Write ``arrays`` ({name: 2-D tensor}) as ``outdir/<name>.npy`` in
+    float32.  When they exceed the byte budget together, every array keeps
+    the same fraction of its rows, picked by a fixed seeded permutation
+    (sorted, so row order is preserved) — the sample depends only on the
+    shapes, never on the values."""
+    os.makedirs(outdir, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    for n, (name, t) in enumerate(sorted(arrays.items())):
+        rows = t.shape[0]
+        if frac < 1.0:
+            keep = max(1, int(rows * frac))
+            g = torch.Generator(device="cpu").manual_seed(DUMP_SAMPLE_SEED + n)
+            idx = torch.randperm(rows, generator=g)[:keep].sort().values
+            t = t[idx.to(t.device)]
+        a = t.detach().to(torch.float32).cpu().contiguous().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def bench_als(args, ctx):
@@ -114,6 +151,14 @@ def bench_als(args, ctx):
     if ctx.device.type == "cuda":
         torch.cuda.synchronize()
     elapsed = ctx.max_scalar(time.perf_counter() - t0)
+
+    if args.dump_outputs and ctx.rank == 0:
+        # what a caller of the timed path receives: the trainer's model
+        # after the last timed step (rank 0's shard rows when distributed)
+        model = trainer.model()
+        dump_outputs(args.dump_outputs,
+                     {"user_factors": model.user_factors,
+                      "item_factors": model.item_factors})
 
     total_nnz = ratings_pg * world
     ms_per_step = elapsed / args.steps * 1000.0
@@ -184,7 +229,7 @@ def main(argv=None):
 
     als = bench_als(args, ctx)
     extra = {}
-    if not args.no_svm:
+    if args.full and not args.no_svm:
         extra = bench_svm(args, ctx)
 
     if ctx.rank == 0:

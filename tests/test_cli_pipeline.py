@@ -286,7 +286,7 @@ def test_driver_bench_launch_contract(tmp_path, world):
              "--steps", "2", "--warmup", "1", "--device", "cpu",
              "--users-per-gpu", "300", "--items", "200",
              "--ratings-per-gpu", "5000", "--rank", "16",
-             "--svm-rows-per-gpu", "400"],
+             "--svm-rows-per-gpu", "400", "--full"],
             capture_output=True, text=True, timeout=500, env=env)
         if res.returncode == 0:
             break

@@ -84,3 +84,44 @@ def test_overlap_force_matches_plain_gpu(gpu):
     di = (res["off"][1] - res["force"][1]).abs().max()
     # same math, different launch slabs/ordering -> tiny reorder noise
     assert du < 1e-3 and di < 1e-3, (du, di)
+
+
+def test_bench_dump_outputs_gpu(gpu, tmp_path, capsys):
+    """bench.py --dump-outputs on the native path: the .npy files hold the
+    factors of the last timed step, i.e. what a trainer fed the same seeded
+    inputs returns after warmup + steps * iters-per-step iterations."""
+    import json
+
+    import numpy as np
+
+    import bench
+    from flink_ms_amd.data.ratings import RatingsShape, synthetic_ratings
+    from flink_ms_amd.models.als import ALSConfig, ALSTrainer
+    nu, ni, nnz, k = 3001, 1203, 120_000, 64
+    out = tmp_path / "dump"
+    rc = bench.main(["--gpus", "1", "--steps", "2", "--warmup", "1",
+                     "--iters-per-step", "2", "--rank", str(k),
+                     "--users-per-gpu", str(nu), "--items", str(ni),
+                     "--ratings-per-gpu", str(nnz),
+                     "--dump-outputs", str(out)])
+    assert rc == 0
+    line = [ln for ln in capsys.readouterr().out.splitlines()
+            if ln.startswith("{")][-1]
+    d = json.loads(line)
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert d["dtype"] == "bf16+fp8-factors"
+    assert not any(key.startswith("svm_") for key in d["config"])
+
+    u, i, r = synthetic_ratings(RatingsShape(nu, ni, nnz), seed=42)
+    tr = ALSTrainer(ALSConfig(iterations=5, num_factors=k, lambda_=0.9,
+                              seed=42, factor_dtype="fp8"))
+    tr.ctx.device = gpu
+    tr.setup(u.long(), i.long(), r, nu, ni)
+    m = tr.fit()
+    for name, ref in (("user_factors", m.user_factors),
+                      ("item_factors", m.item_factors)):
+        x = np.load(out / f"{name}.npy")
+        assert x.dtype == np.float32 and x.shape == tuple(ref.shape)
+        assert np.isfinite(x).all()
+        # same kernels on the same inputs: no tolerance beyond fp32 noise
+        assert np.abs(x - ref.cpu().numpy()).max() < 1e-3

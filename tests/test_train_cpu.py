@@ -101,7 +101,7 @@ def test_bench_json_contract(capsys):
     rc = bench.main(["--device", "cpu", "--steps", "1", "--warmup", "0",
                      "--rank", "8", "--ratings-per-gpu", "1500",
                      "--users-per-gpu", "100", "--items", "60",
-                     "--svm-rows-per-gpu", "250"])
+                     "--svm-rows-per-gpu", "250", "--full"])
     assert rc == 0
     line = [ln for ln in capsys.readouterr().out.splitlines()
             if ln.startswith("{")][-1]
@@ -113,9 +113,73 @@ def test_bench_json_contract(capsys):
     assert out["higher_is_better"] is True and out["scaling"] == "weak"
     assert out["data"] == "synthetic" and out["value"] > 0
     assert out["config"]["global_batch"] == 1500 * out["n_gpus"]
-    # the CoCoA-SVM secondary metric rides in config BY DEFAULT (no --svm)
+    # the CoCoA-SVM secondary metric rides in config under --full
     assert out["config"]["svm_samples_per_sec"] > 0
     assert out["config"]["timed_region_s"] > 0
+
+
+_BENCH_TINY = ["--device", "cpu", "--steps", "2", "--warmup", "1",
+               "--rank", "8", "--ratings-per-gpu", "1500",
+               "--users-per-gpu", "100", "--items", "60"]
+
+
+def test_bench_plain_run_is_lean(capsys):
+    """A plain run times only the ALS flagship: same headline keys, no
+    secondary (SVM) figures — those live behind --full."""
+    import json
+
+    import bench
+    assert bench.main(_BENCH_TINY) == 0
+    line = [ln for ln in capsys.readouterr().out.splitlines()
+            if ln.startswith("{")][-1]
+    out = json.loads(line)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype",
+                "ms_per_step"):
+        assert key in out, key
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert abs(out["ms_per_step"] * out["steps"]
+               - out["config"]["timed_region_s"] * 1e3) < 1e-6
+    assert not any(k.startswith("svm_") for k in out["config"])
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the last timed step's factors as float32 .npy;
+    the same arguments give the same inputs, hence (on the deterministic
+    CPU path) identical files; another seed gives other values."""
+    import numpy as np
+
+    import bench
+    a, b, c = tmp_path / "a", tmp_path / "b", tmp_path / "c"
+    assert bench.main(_BENCH_TINY + ["--dump-outputs", str(a)]) == 0
+    assert bench.main(_BENCH_TINY + ["--dump-outputs", str(b)]) == 0
+    assert bench.main(_BENCH_TINY + ["--seed", "7",
+                                     "--dump-outputs", str(c)]) == 0
+    assert sorted(p.name for p in a.iterdir()) == ["item_factors.npy",
+                                                   "user_factors.npy"]
+    for name, rows in (("user_factors", 100), ("item_factors", 60)):
+        x = np.load(a / f"{name}.npy")
+        assert x.dtype == np.float32 and x.shape == (rows, 8)
+        assert np.isfinite(x).all() and np.abs(x).max() > 0
+        assert np.array_equal(x, np.load(b / f"{name}.npy"))
+        assert not np.array_equal(x, np.load(c / f"{name}.npy"))
+
+
+def test_bench_dump_outputs_budget(tmp_path, monkeypatch):
+    """Outputs over the byte budget are cut to a fixed seeded row sample:
+    same rows every run, original row order kept."""
+    import numpy as np
+
+    import bench
+    t = torch.arange(1000, dtype=torch.float32).repeat_interleave(4).view(1000, 4)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4000)
+    bench.dump_outputs(str(tmp_path / "a"), {"x": t, "y": t[:500] * 2})
+    bench.dump_outputs(str(tmp_path / "b"), {"x": t, "y": t[:500] * 2})
+    x, y = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "y.npy")
+    assert x.nbytes + y.nbytes <= 4000 and len(x) > 0 and len(y) > 0
+    assert (np.diff(x[:, 0]) > 0).all()          # sorted distinct source rows
+    assert (x == x[:, :1]).all()                 # whole rows, unmixed
+    assert np.array_equal(x, np.load(tmp_path / "b" / "x.npy"))
+    assert np.array_equal(y, np.load(tmp_path / "b" / "y.npy"))
 
 
 def test_ratings_loader_delimiters(tmp_path):
