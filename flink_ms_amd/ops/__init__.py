@@ -89,6 +89,26 @@ def fp8_rating_pair(r: torch.Tensor) -> torch.Tensor:
 
 # -------------------------------------------------------------------- ALS
 
+# Lane-broadcast variants of the k<=64 register LDL (WREG_BC_* in
+# als_kernels.hip).  All of them compute bit-identical results; the
+# non-default ones are measured ablations (docs/KERNELS.md, round 3).
+_WREG_BROADCAST = {"shfl": 0, "panel": 1, "subst": 2, "readlane": 3}
+
+
+def _wreg_broadcast() -> int:
+    """``FMA_WREG_BROADCAST`` selects the variant: ``readlane`` (default:
+    v_readlane broadcasts, branch-free substitutions), ``shfl`` (the LDS
+    shuffle path), or the ladder steps ``panel`` / ``subst`` (wave-fused
+    kernel only)."""
+    import os as _os
+    name = _os.environ.get("FMA_WREG_BROADCAST", "readlane")
+    if name not in _WREG_BROADCAST:
+        raise ValueError(
+            f"FMA_WREG_BROADCAST={name!r}: expected one of "
+            f"{sorted(_WREG_BROADCAST)}")
+    return _WREG_BROADCAST[name]
+
+
 def als_solve_side(
     csr: CSR,
     other_factors: torch.Tensor,
@@ -108,7 +128,7 @@ def als_solve_side(
       straight into the register LDL's lower-triangle C-fragments (one
       wave per entity, no A in HBM, no barriers; split-wave dual-chunk
       staging).  ``FMA_WAVEFUSED_DB=1`` selects the software-pipelined
-      ablation.
+      ablation, ``FMA_WREG_BROADCAST=shfl`` the LDS-shuffle broadcasts.
     - k > 64 (or ``fused=True``): the block-fused kernel (triangular LDS
       A image, 4 blocks/CU).
     - ``slab_rows``: the modular gramian -> batched-solve path, kept for
@@ -154,11 +174,12 @@ def als_solve_side(
             if fp8 and _os.environ.get("FMA_WAVEFUSED_DB") == "1":
                 ops.als_solve_wavefused_db(csr.indptr, csr.indices,
                                            csr.values, fac, out, ob, o8,
-                                           ro, float(reg), _stream())
+                                           ro, float(reg), _stream(),
+                                           _wreg_broadcast())
             else:
                 ops.als_solve_wavefused(csr.indptr, csr.indices, csr.values,
                                         fac, out, ob, o8, ro, float(reg),
-                                        _stream())
+                                        _stream(), _wreg_broadcast())
         else:
             # slab the normal equations: A is nrows*k*k fp32, which at the
             # 1B-rating configs would exceed HBM if materialized whole.
@@ -191,7 +212,7 @@ def als_solve_side(
                 o8s = o8[s:e] if o8.numel() > 0 else o8
                 if k <= 64:
                     ops.ldl_solve_wave_reg(As, bs, out[s:e], obs, o8s,
-                                           _stream())
+                                           _stream(), _wreg_broadcast())
                 else:
                     ops.cholesky_solve(As, bs, out[s:e], _stream())
                     if out_bf16 is not None:
@@ -238,7 +259,7 @@ def als_solve_chunk(
         if k <= 64:
             ops.als_solve_wavefused(ip, csr.indices, csr.values, fac,
                                     out_f32, ob, o8, ids, float(reg),
-                                    _stream())
+                                    _stream(), _wreg_broadcast())
         elif fp8:
             ops.als_solve_fused_fp8(ip, csr.indices, csr.values, fac,
                                     out_f32, o8, ids, float(reg), _stream())

@@ -595,28 +595,81 @@ DEV_INLINE void wreg_trail(f32x4* T, const float* scr, const float* ndk,
     }
 }
 
-template <int KT, int PI>
+// Lane broadcasts of the panel factorization and the substitutions.  Every
+// source lane is a compile-time constant, so the broadcast can be a
+// v_readlane (VALU -> SGPR, no LDS pipe, no lgkmcnt wait; it ignores EXEC,
+// and the source lanes are always live) instead of the ds_bpermute that
+// __shfl lowers to.  BC selects how far the broadcasts leave the LDS; the
+// arithmetic (operands, order, contraction) is the same at every level,
+// so all levels are bit-identical:
+//   WREG_BC_SHFL   the __shfl code path, kept as the measured baseline
+//   WREG_BC_PANEL  readlane in the panel factorization only
+//   WREG_BC_SUBST  + readlane in both substitutions (one broadcast of the
+//                  per-lane product x0*id0 in the forward step)
+//   WREG_BC_HOIST  + branch-free substitution steps, the block's L entries
+//                  read ahead of the serial chain (the default)
+#define WREG_BC_SHFL 0
+#define WREG_BC_PANEL 1
+#define WREG_BC_SUBST 2
+#define WREG_BC_HOIST 3
+// L entries read ahead per group in the branch-free substitutions: T[] is
+// still live there, so the group is sized to the kernel's 96-VGPR budget
+#define WREG_HOIST 8
+
+template <bool RL>
+DEV_INLINE float wreg_bcast(float v, int src) {
+    if constexpr (RL)
+        return __builtin_bit_cast(
+            float,
+            __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
+    else
+        return __shfl(v, src, WAVE);
+}
+
+// Rounding of the panel's rank-1 updates, pinned.  Written as
+// seg[cc] -= lscl * colj the contraction was the compiler's choice: its
+// SLP pass paired most of the products across consecutive pivots into
+// packed multiplies (then subtracted, two roundings) and fused the rest
+// into FMAs -- and it pairs differently once the broadcast operand is a
+// scalar register.  The split below is the one every instantiation of the
+// shuffle path compiled to (read off the optimized IR), spelled out so
+// that all broadcast variants, and later compilers, round identically.
+constexpr bool wreg_update_unfused(int jj, int cc) {
+    if (jj == 0) return cc >= 2 && cc <= 10 && cc % 2 == 0;
+    return cc <= (jj + 10 < 14 ? jj + 10 : 14);
+}
+
+DEV_INLINE float wreg_mul_sub(float acc, float a, float b) {
+#pragma clang fp contract(off)
+    return acc - a * b;
+}
+
+template <int KT, int PI, int BC>
 DEV_INLINE void wreg_panels(f32x4* T, float* scr, int lane, int g4, int li,
                             float& d0) {
     if constexpr (PI < KT) {
         constexpr int K = KT * 16;
         constexpr int P0 = 16 * PI;
+        constexpr bool RL = BC >= WREG_BC_PANEL;
         wreg_dump_col<KT, PI, PI>(T, scr, g4, li);
         WREG_FENCE();
-        // register factorization of the panel: lane = row P0+lane
+        // register factorization of the panel: lane = row P0+lane; lanes
+        // 0..15 (always inside the mask) hold the diagonal block
         if (lane < K - P0) {
             float seg[16];
 #pragma unroll
             for (int cc = 0; cc < 16; ++cc) seg[cc] = scr[lane * 17 + cc];
 #pragma unroll
             for (int jj = 0; jj < 15; ++jj) {
-                const float dj = __shfl(seg[jj], jj, WAVE);
+                const float dj = wreg_bcast<RL>(seg[jj], jj);
                 const float dinv = dj > 0.0f ? 1.0f / dj : 0.0f;
                 const float lscl = seg[jj] * dinv;
 #pragma unroll
                 for (int cc = jj + 1; cc < 16; ++cc) {
-                    const float colj = __shfl(seg[jj], cc, WAVE);
-                    seg[cc] -= lscl * colj;
+                    const float colj = wreg_bcast<RL>(seg[jj], cc);
+                    seg[cc] = wreg_update_unfused(jj, cc)
+                                  ? wreg_mul_sub(seg[cc], lscl, colj)
+                                  : __builtin_fmaf(-lscl, colj, seg[cc]);
                 }
             }
 #pragma unroll
@@ -636,11 +689,11 @@ DEV_INLINE void wreg_panels(f32x4* T, float* scr, int lane, int g4, int li,
             }
             wreg_trail<KT, PI, PI + 1, PI + 1>(T, scr, ndk, g4, li);
         }
-        wreg_panels<KT, PI + 1>(T, scr, lane, g4, li, d0);
+        wreg_panels<KT, PI + 1, BC>(T, scr, lane, g4, li, d0);
     }
 }
 
-template <int KT, int J>
+template <int KT, int J, int BC>
 DEV_INLINE void wreg_forward(const f32x4* T, float* scr, float& x0,
                              float id0, int lane, int g4, int li) {
     if constexpr (J < KT) {
@@ -648,15 +701,47 @@ DEV_INLINE void wreg_forward(const f32x4* T, float* scr, float& x0,
         constexpr int B0 = 16 * J;
         wreg_dump_col<KT, J, J>(T, scr, g4, li);
         WREG_FENCE();
+        if constexpr (BC >= WREG_BC_HOIST) {
+            // every lane reads a row of the dumped panel (clamped into the
+            // rows dump_col wrote) and the step keeps or drops the RESULT:
+            // no exec region around the read, so a group's reads issue
+            // ahead of the chain.  Selecting the result, not the L entry,
+            // keeps idle lanes untouched whatever the broadcast value is
+            // (a zeroed L entry would still flip a -0.0 or spread a NaN).
+            const int lrow = (lane < K ? lane : K - 1) - B0;
+            const float* lp = scr + (lrow > 0 ? lrow : 0) * 17;
+            constexpr int NS = (K - 1 - B0 < 16) ? K - 1 - B0 : 16;
 #pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const int j = B0 + t;
-            if (j >= K - 1) break;
-            const float zj = __shfl(x0, j, WAVE) * __shfl(id0, j, WAVE);
-            if (lane > j && lane < K)
-                x0 -= scr[(lane - B0) * 17 + t] * zj;
+            for (int t0 = 0; t0 < NS; t0 += WREG_HOIST) {
+                float l[WREG_HOIST];
+#pragma unroll
+                for (int u = 0; u < WREG_HOIST; ++u)
+                    if (t0 + u < NS) l[u] = lp[t0 + u];
+#pragma unroll
+                for (int u = 0; u < WREG_HOIST; ++u) {
+                    if (t0 + u < NS) {
+                        const int j = B0 + t0 + u;
+                        const float zj = wreg_bcast<true>(x0 * id0, j);
+                        const float xn = __builtin_fmaf(-l[u], zj, x0);
+                        x0 = (lane > j && lane < K) ? xn : x0;
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const int j = B0 + t;
+                if (j >= K - 1) break;
+                float zj;
+                if constexpr (BC >= WREG_BC_SUBST)
+                    zj = wreg_bcast<true>(x0 * id0, j);
+                else
+                    zj = __shfl(x0, j, WAVE) * __shfl(id0, j, WAVE);
+                if (lane > j && lane < K)
+                    x0 = __builtin_fmaf(-scr[(lane - B0) * 17 + t], zj, x0);
+            }
         }
-        wreg_forward<KT, J + 1>(T, scr, x0, id0, lane, g4, li);
+        wreg_forward<KT, J + 1, BC>(T, scr, x0, id0, lane, g4, li);
     }
 }
 
@@ -671,22 +756,47 @@ DEV_INLINE void wreg_dump_row(const f32x4* T, float* scr, int g4, int li) {
     }
 }
 
-template <int KT, int I>
+template <int KT, int I, int BC>
 DEV_INLINE void wreg_backward(const f32x4* T, float* scr, float& x0,
                               float id0, int lane, int g4, int li) {
     if constexpr (I >= 0) {
         constexpr int B0 = 16 * I;
         wreg_dump_row<KT, I, 0>(T, scr, g4, li);
         WREG_FENCE();
+        if constexpr (BC >= WREG_BC_HOIST) {
+            // t*65 + lane <= 15*65 + 63 stays inside the 1040-float
+            // scratch for every lane; lanes >= c read stale words that
+            // the result select drops
+            constexpr int T0 = (I == 0) ? 1 : 0;    // c = B0 + t >= 1
 #pragma unroll
-        for (int t = 15; t >= 0; --t) {
-            const int c = B0 + t;
-            if (c < 1) break;
-            const float xc = __shfl(x0, c, WAVE);
-            if (lane < c)
-                x0 -= scr[t * 65 + lane] * id0 * xc;
+            for (int t1 = 16; t1 > T0; t1 -= WREG_HOIST) {
+                float m[WREG_HOIST];
+#pragma unroll
+                for (int u = 0; u < WREG_HOIST; ++u)
+                    if (t1 - 1 - u >= T0)
+                        m[u] = scr[(t1 - 1 - u) * 65 + lane] * id0;
+#pragma unroll
+                for (int u = 0; u < WREG_HOIST; ++u) {
+                    if (t1 - 1 - u >= T0) {
+                        const int c = B0 + t1 - 1 - u;
+                        const float xc = wreg_bcast<true>(x0, c);
+                        const float xn = __builtin_fmaf(-m[u], xc, x0);
+                        x0 = (lane < c) ? xn : x0;
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int t = 15; t >= 0; --t) {
+                const int c = B0 + t;
+                if (c < 1) break;
+                const float xc =
+                    wreg_bcast<(BC >= WREG_BC_SUBST)>(x0, c);
+                if (lane < c)
+                    x0 = __builtin_fmaf(-(scr[t * 65 + lane] * id0), xc, x0);
+            }
         }
-        wreg_backward<KT, I - 1>(T, scr, x0, id0, lane, g4, li);
+        wreg_backward<KT, I - 1, BC>(T, scr, x0, id0, lane, g4, li);
     }
 }
 
@@ -703,7 +813,7 @@ DEV_INLINE void wreg_load_A(f32x4* T, const float* src, int g4, int li) {
     }
 }
 
-template <int KT>
+template <int KT, int BC>
 __launch_bounds__(256)
 __global__ void k_ldl_solve_wave_reg(const float* __restrict__ A_in,
                                      const float* __restrict__ b_in,
@@ -727,11 +837,11 @@ __global__ void k_ldl_solve_wave_reg(const float* __restrict__ A_in,
     wreg_load_A<KT, 0>(T, A_in + e * (long long)(K * K), g4, li);
     float x0 = (lane < K) ? b_in[e * K + lane] : 0.0f;
     float d0 = 1.0f;
-    wreg_panels<KT, 0>(T, scr, lane, g4, li, d0);
+    wreg_panels<KT, 0, BC>(T, scr, lane, g4, li, d0);
     const float id0 = d0 > 0.0f ? 1.0f / d0 : 0.0f;
-    wreg_forward<KT, 0>(T, scr, x0, id0, lane, g4, li);
+    wreg_forward<KT, 0, BC>(T, scr, x0, id0, lane, g4, li);
     x0 *= id0;
-    wreg_backward<KT, KT - 1>(T, scr, x0, id0, lane, g4, li);
+    wreg_backward<KT, KT - 1, BC>(T, scr, x0, id0, lane, g4, li);
     if (lane < K) {
         x_out[e * K + lane] = x0;
         if (x_bf16) x_bf16[e * K + lane] = f2bf(x0);
@@ -742,16 +852,31 @@ __global__ void k_ldl_solve_wave_reg(const float* __restrict__ A_in,
 extern "C" hipError_t fma_ldl_solve_wave_reg(
     int k, const float* A_in, const float* b_in, float* x_out,
     unsigned short* x_bf16, unsigned char* x_fp8, long long nrows,
-    hipStream_t stream) {
+    int variant, hipStream_t stream) {
     if (k % 16 || k < 16 || k > 64 || nrows <= 0) return hipErrorInvalidValue;
+    // the intermediate ladder levels exist for k_als_solve_wavefused only
+    if (variant != WREG_BC_SHFL && variant != WREG_BC_HOIST)
+        return hipErrorInvalidValue;
     dim3 grid((unsigned)((nrows + 3) / 4)), block(256);
+#define WR_CASE(KT)                                                           \
+    case KT:                                                                  \
+        if (variant == WREG_BC_SHFL)                                          \
+            k_ldl_solve_wave_reg<KT, WREG_BC_SHFL><<<grid, block, 0,          \
+                                                     stream>>>(               \
+                A_in, b_in, x_out, x_bf16, x_fp8, nrows);                     \
+        else                                                                  \
+            k_ldl_solve_wave_reg<KT, WREG_BC_HOIST><<<grid, block, 0,         \
+                                                      stream>>>(              \
+                A_in, b_in, x_out, x_bf16, x_fp8, nrows);                     \
+        break;
     switch (k / 16) {
-        case 1: k_ldl_solve_wave_reg<1><<<grid, block, 0, stream>>>(A_in, b_in, x_out, x_bf16, x_fp8, nrows); break;
-        case 2: k_ldl_solve_wave_reg<2><<<grid, block, 0, stream>>>(A_in, b_in, x_out, x_bf16, x_fp8, nrows); break;
-        case 3: k_ldl_solve_wave_reg<3><<<grid, block, 0, stream>>>(A_in, b_in, x_out, x_bf16, x_fp8, nrows); break;
-        case 4: k_ldl_solve_wave_reg<4><<<grid, block, 0, stream>>>(A_in, b_in, x_out, x_bf16, x_fp8, nrows); break;
+        WR_CASE(1)
+        WR_CASE(2)
+        WR_CASE(3)
+        WR_CASE(4)
         default: return hipErrorInvalidValue;
     }
+#undef WR_CASE
     return hipGetLastError();
 }
 
@@ -903,7 +1028,7 @@ DEV_INLINE void stage_commit(const StagedRegs<KT, FP8>& sr, char* buf,
 
 // Double-buffered wave-fused ALS solve (fp8, k <= 64): same math as
 // k_als_solve_wavefused, software-pipelined staging.
-template <int KT>
+template <int KT, int BC>
 __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(4)))
 __global__ void k_als_solve_wavefused_db(const long long* __restrict__ indptr,
@@ -978,11 +1103,11 @@ __global__ void k_als_solve_wavefused_db(const long long* __restrict__ indptr,
     WREG_FENCE();
     wavefused_diag<KT>(T, reg * (float)n, g4, li);
     float d0 = 1.0f;
-    wreg_panels<KT, 0>(T, scr, lane, g4, li, d0);
+    wreg_panels<KT, 0, BC>(T, scr, lane, g4, li, d0);
     const float id0 = d0 > 0.0f ? 1.0f / d0 : 0.0f;
-    wreg_forward<KT, 0>(T, scr, x0, id0, lane, g4, li);
+    wreg_forward<KT, 0, BC>(T, scr, x0, id0, lane, g4, li);
     x0 *= id0;
-    wreg_backward<KT, KT - 1>(T, scr, x0, id0, lane, g4, li);
+    wreg_backward<KT, KT - 1, BC>(T, scr, x0, id0, lane, g4, li);
     if (lane < K) {
         out_f32[e * K + lane] = x0;
         if (out_bf16) out_bf16[e * K + lane] = f2bf(x0);
@@ -994,25 +1119,43 @@ extern "C" hipError_t fma_als_solve_wavefused_db(
     int k, const long long* indptr, const int* indices, const float* values,
     const void* factors, float* out_f32, unsigned short* out_bf16,
     unsigned char* out_fp8, const int* row_order, long long nrows,
-    float reg, hipStream_t stream) {
+    float reg, int variant, hipStream_t stream) {
     if (k % 16 || k < 16 || k > 64 || nrows <= 0) return hipErrorInvalidValue;
+    if (variant != WREG_BC_SHFL && variant != WREG_BC_HOIST)
+        return hipErrorInvalidValue;
     dim3 grid((unsigned)((nrows + 3) / 4)), block(256);
+#define DB_CASE(KT)                                                           \
+    case KT:                                                                  \
+        if (variant == WREG_BC_SHFL)                                          \
+            k_als_solve_wavefused_db<KT, WREG_BC_SHFL><<<grid, block, 0,      \
+                                                         stream>>>(           \
+                indptr, indices, values, factors, out_f32, out_bf16,          \
+                out_fp8, row_order, nrows, reg);                              \
+        else                                                                  \
+            k_als_solve_wavefused_db<KT, WREG_BC_HOIST><<<grid, block, 0,     \
+                                                          stream>>>(          \
+                indptr, indices, values, factors, out_f32, out_bf16,          \
+                out_fp8, row_order, nrows, reg);                              \
+        break;
     switch (k / 16) {
-        case 1: k_als_solve_wavefused_db<1><<<grid, block, 0, stream>>>(indptr, indices, values, factors, out_f32, out_bf16, out_fp8, row_order, nrows, reg); break;
-        case 2: k_als_solve_wavefused_db<2><<<grid, block, 0, stream>>>(indptr, indices, values, factors, out_f32, out_bf16, out_fp8, row_order, nrows, reg); break;
-        case 3: k_als_solve_wavefused_db<3><<<grid, block, 0, stream>>>(indptr, indices, values, factors, out_f32, out_bf16, out_fp8, row_order, nrows, reg); break;
-        case 4: k_als_solve_wavefused_db<4><<<grid, block, 0, stream>>>(indptr, indices, values, factors, out_f32, out_bf16, out_fp8, row_order, nrows, reg); break;
+        DB_CASE(1)
+        DB_CASE(2)
+        DB_CASE(3)
+        DB_CASE(4)
         default: return hipErrorInvalidValue;
     }
+#undef DB_CASE
     return hipGetLastError();
 }
 
-template <int KT, bool FP8>
+template <int KT, bool FP8, int BC>
 __launch_bounds__(256)
 // waves_per_eu(5): 96 VGPRs with ~12-17 spilled (52-60 B/lane scratch) buys
 // a 5th wave/SIMD over the natural 105-reg allocation — measured 3.23 ->
 // 2.65 ms/iter on the rank-64 headline (the spill traffic hides behind the
-// same gather stalls the extra wave fills)
+// same gather stalls the extra wave fills).  With the readlane broadcasts
+// (BC >= WREG_BC_PANEL) the panel's operands sit in SGPRs and the same cap
+// is met at 95 VGPRs with no spill at all.
 __attribute__((amdgpu_waves_per_eu(5)))
 __global__ void k_als_solve_wavefused(const long long* __restrict__ indptr,
                                       const int* __restrict__ indices,
@@ -1110,11 +1253,11 @@ __global__ void k_als_solve_wavefused(const long long* __restrict__ indptr,
     wavefused_diag<KT>(T, reg * (float)n, g4, li);
     // in-register LDL + substitution (shared with k_ldl_solve_wave_reg)
     float d0 = 1.0f;
-    wreg_panels<KT, 0>(T, scr, lane, g4, li, d0);
+    wreg_panels<KT, 0, BC>(T, scr, lane, g4, li, d0);
     const float id0 = d0 > 0.0f ? 1.0f / d0 : 0.0f;
-    wreg_forward<KT, 0>(T, scr, x0, id0, lane, g4, li);
+    wreg_forward<KT, 0, BC>(T, scr, x0, id0, lane, g4, li);
     x0 *= id0;
-    wreg_backward<KT, KT - 1>(T, scr, x0, id0, lane, g4, li);
+    wreg_backward<KT, KT - 1, BC>(T, scr, x0, id0, lane, g4, li);
     if (lane < K) {
         out_f32[e * K + lane] = x0;
         if (out_bf16) out_bf16[e * K + lane] = f2bf(x0);
@@ -1126,19 +1269,30 @@ extern "C" hipError_t fma_als_solve_wavefused(
     int k, int fp8, const long long* indptr, const int* indices,
     const float* values, const void* factors, float* out_f32,
     unsigned short* out_bf16, unsigned char* out_fp8, const int* row_order,
-    long long nrows, float reg, hipStream_t stream) {
+    long long nrows, float reg, int variant, hipStream_t stream) {
     if (k % 16 || k < 16 || k > 64 || nrows <= 0) return hipErrorInvalidValue;
     dim3 grid((unsigned)((nrows + 3) / 4)), block(256);
-#define WF_CASE(KT)                                                           \
-    case KT:                                                                  \
+#define WF_LAUNCH(KT, BC)                                                     \
+    do {                                                                      \
         if (fp8)                                                              \
-            k_als_solve_wavefused<KT, true><<<grid, block, 0, stream>>>(      \
+            k_als_solve_wavefused<KT, true, BC><<<grid, block, 0, stream>>>(  \
                 indptr, indices, values, factors, out_f32, out_bf16,          \
                 out_fp8, row_order, nrows, reg);                              \
         else                                                                  \
-            k_als_solve_wavefused<KT, false><<<grid, block, 0, stream>>>(     \
+            k_als_solve_wavefused<KT, false, BC><<<grid, block, 0,            \
+                                                   stream>>>(                 \
                 indptr, indices, values, factors, out_f32, out_bf16,          \
                 out_fp8, row_order, nrows, reg);                              \
+    } while (0)
+#define WF_CASE(KT)                                                           \
+    case KT:                                                                  \
+        switch (variant) {                                                    \
+            case WREG_BC_SHFL: WF_LAUNCH(KT, WREG_BC_SHFL); break;            \
+            case WREG_BC_PANEL: WF_LAUNCH(KT, WREG_BC_PANEL); break;          \
+            case WREG_BC_SUBST: WF_LAUNCH(KT, WREG_BC_SUBST); break;          \
+            case WREG_BC_HOIST: WF_LAUNCH(KT, WREG_BC_HOIST); break;          \
+            default: return hipErrorInvalidValue;                             \
+        }                                                                     \
         break;
     switch (k / 16) {
         WF_CASE(1)
@@ -1148,6 +1302,7 @@ extern "C" hipError_t fma_als_solve_wavefused(
         default: return hipErrorInvalidValue;
     }
 #undef WF_CASE
+#undef WF_LAUNCH
     return hipGetLastError();
 }
 

@@ -58,13 +58,13 @@ int fma_als_solve_wavefused_db(int k, const int64_t* indptr,
                                unsigned short* out_bf16,
                                unsigned char* out_fp8,
                                const int* row_order, int64_t nrows,
-                               float reg, void* stream);
+                               float reg, int variant, void* stream);
 int fma_als_solve_wavefused(int k, int fp8, const int64_t* indptr,
                             const int* indices, const float* values,
                             const void* factors, float* out_f32,
                             unsigned short* out_bf16, unsigned char* out_fp8,
                             const int* row_order, int64_t nrows, float reg,
-                            void* stream);
+                            int variant, void* stream);
 int fma_als_solve_wavefused2(int k, const int64_t* indptr,
                              const int* indices, const float* values,
                              const unsigned char* factors, float* out_f32,
@@ -76,7 +76,7 @@ int fma_ldl_solve_wave(int k, const float* A_in, const float* b_in,
 int fma_ldl_solve_wave_reg(int k, const float* A_in, const float* b_in,
                            float* x_out, unsigned short* x_bf16,
                            unsigned char* x_fp8, int64_t nrows,
-                           void* stream);
+                           int variant, void* stream);
 int fma_mfma_probe_f32(const float* A, const float* B, float* D, void* stream);
 int fma_mfma_probe_bf16(const unsigned short* Xt, const unsigned short* Yt,
                         float* C, void* stream);
@@ -360,13 +360,22 @@ void cholesky_solve_ph(torch::Tensor A, torch::Tensor b, torch::Tensor x,
               "cholesky_solve_ph");
 }
 
+// Lane-broadcast variant of the register LDL (WREG_BC_* in
+// als_kernels.hip): 0 = the __shfl path kept as the measured baseline,
+// 3 = readlane broadcasts + branch-free substitutions (the default), 1 and
+// 2 = the intermediate ladder steps (k_als_solve_wavefused only).  Every
+// variant computes bit-identical results.  Each binding below also keeps
+// its variant-less signature, which runs the default.
+constexpr int64_t kBroadcastShfl = 0;
+constexpr int64_t kBroadcastDefault = 3;
+
 // single-kernel k<=64 path: Gramian + register LDL in one wave per entity
 // (no A materialization in HBM).  factors dtype selects bf16 vs e4m3.
-void als_solve_wavefused(torch::Tensor indptr, torch::Tensor indices,
-                         torch::Tensor values, torch::Tensor factors,
-                         torch::Tensor out_f32, torch::Tensor out_bf16,
-                         torch::Tensor out_fp8, torch::Tensor row_order,
-                         double reg, int64_t stream) {
+void als_solve_wavefused_v(torch::Tensor indptr, torch::Tensor indices,
+                           torch::Tensor values, torch::Tensor factors,
+                           torch::Tensor out_f32, torch::Tensor out_bf16,
+                           torch::Tensor out_fp8, torch::Tensor row_order,
+                           double reg, int64_t stream, int64_t variant) {
     check_t(indptr, torch::kInt64, "indptr");
     check_t(indices, torch::kInt32, "indices");
     check_t(values, torch::kFloat32, "values");
@@ -394,16 +403,26 @@ void als_solve_wavefused(torch::Tensor indptr, torch::Tensor indices,
                   indices.data_ptr<int>(), values.data_ptr<float>(),
                   factors.data_ptr(), out_f32.data_ptr<float>(), ob, o8,
                   order_ptr(row_order, nrows), nrows, (float)reg,
-                  (void*)stream),
+                  (int)variant, (void*)stream),
               "als_solve_wavefused");
 }
 
+void als_solve_wavefused(torch::Tensor indptr, torch::Tensor indices,
+                         torch::Tensor values, torch::Tensor factors,
+                         torch::Tensor out_f32, torch::Tensor out_bf16,
+                         torch::Tensor out_fp8, torch::Tensor row_order,
+                         double reg, int64_t stream) {
+    als_solve_wavefused_v(indptr, indices, values, factors, out_f32,
+                          out_bf16, out_fp8, row_order, reg, stream,
+                          kBroadcastDefault);
+}
+
 // double-buffered variant (fp8 only): software-pipelined staging
-void als_solve_wavefused_db(torch::Tensor indptr, torch::Tensor indices,
-                            torch::Tensor values, torch::Tensor factors,
-                            torch::Tensor out_f32, torch::Tensor out_bf16,
-                            torch::Tensor out_fp8, torch::Tensor row_order,
-                            double reg, int64_t stream) {
+void als_solve_wavefused_db_v(torch::Tensor indptr, torch::Tensor indices,
+                              torch::Tensor values, torch::Tensor factors,
+                              torch::Tensor out_f32, torch::Tensor out_bf16,
+                              torch::Tensor out_fp8, torch::Tensor row_order,
+                              double reg, int64_t stream, int64_t variant) {
     check_t(indptr, torch::kInt64, "indptr");
     check_t(indices, torch::kInt32, "indices");
     check_t(values, torch::kFloat32, "values");
@@ -422,8 +441,18 @@ void als_solve_wavefused_db(torch::Tensor indptr, torch::Tensor indices,
                   values.data_ptr<float>(), factors.data_ptr(),
                   out_f32.data_ptr<float>(), ob, o8,
                   order_ptr(row_order, nrows), nrows, (float)reg,
-                  (void*)stream),
+                  (int)variant, (void*)stream),
               "als_solve_wavefused_db");
+}
+
+void als_solve_wavefused_db(torch::Tensor indptr, torch::Tensor indices,
+                            torch::Tensor values, torch::Tensor factors,
+                            torch::Tensor out_f32, torch::Tensor out_bf16,
+                            torch::Tensor out_fp8, torch::Tensor row_order,
+                            double reg, int64_t stream) {
+    als_solve_wavefused_db_v(indptr, indices, values, factors, out_f32,
+                             out_bf16, out_fp8, row_order, reg, stream,
+                             kBroadcastDefault);
 }
 
 // wave-pair fused path for 64 < k <= 128 (fp8 gathers only)
@@ -466,15 +495,22 @@ void ldl_solve_wave(torch::Tensor A, torch::Tensor b, torch::Tensor x,
 }
 
 // register-resident v2 (A in MFMA fragments, panel scratch in LDS)
-void ldl_solve_wave_reg(torch::Tensor A, torch::Tensor b, torch::Tensor x,
-                        torch::Tensor x_bf16, torch::Tensor x_fp8,
-                        int64_t stream) {
+void ldl_solve_wave_reg_v(torch::Tensor A, torch::Tensor b, torch::Tensor x,
+                          torch::Tensor x_bf16, torch::Tensor x_fp8,
+                          int64_t stream, int64_t variant) {
     unsigned short* xb = x_bf16.numel() > 0 ? bf16_ptr_mut(x_bf16) : nullptr;
     unsigned char* x8 = x_fp8.numel() > 0 ? fp8_ptr_mut(x_fp8) : nullptr;
     check_hip(fma_ldl_solve_wave_reg((int)A.size(1), A.data_ptr<float>(),
                                      b.data_ptr<float>(), x.data_ptr<float>(),
-                                     xb, x8, A.size(0), (void*)stream),
+                                     xb, x8, A.size(0), (int)variant,
+                                     (void*)stream),
               "ldl_solve_wave_reg");
+}
+
+void ldl_solve_wave_reg(torch::Tensor A, torch::Tensor b, torch::Tensor x,
+                        torch::Tensor x_bf16, torch::Tensor x_fp8,
+                        int64_t stream) {
+    ldl_solve_wave_reg_v(A, b, x, x_bf16, x_fp8, stream, kBroadcastDefault);
 }
 
 void cholesky_solve(torch::Tensor A, torch::Tensor b, torch::Tensor x,
@@ -643,13 +679,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gramian", &gramian);
     m.def("gramian_fp8", &gramian_fp8);
     m.def("als_solve_fused_fp8", &als_solve_fused_fp8);
+    m.attr("BROADCAST_SHFL") = kBroadcastShfl;
+    m.attr("BROADCAST_DEFAULT") = kBroadcastDefault;
     m.def("als_solve_wavefused", &als_solve_wavefused);
+    m.def("als_solve_wavefused", &als_solve_wavefused_v);
     m.def("als_solve_wavefused2", &als_solve_wavefused2);
     m.def("als_solve_wavefused_db", &als_solve_wavefused_db);
+    m.def("als_solve_wavefused_db", &als_solve_wavefused_db_v);
     m.def("cholesky_solve", &cholesky_solve);
     m.def("cholesky_solve_ph", &cholesky_solve_ph);
     m.def("ldl_solve_wave", &ldl_solve_wave);
     m.def("ldl_solve_wave_reg", &ldl_solve_wave_reg);
+    m.def("ldl_solve_wave_reg", &ldl_solve_wave_reg_v);
     m.def("sdca_pass", &sdca_pass);
     m.def("svm_margins", &svm_margins);
     m.def("predict_dot", &predict_dot);
