@@ -342,6 +342,15 @@ def sdca_pass(
     reference.sdca_epoch_reference(csr, y, alpha, v, lamb, n_global, perm)
 
 
+def sdca_num_waves(nrows: int) -> int:
+    """Waves one GPU ``sdca_pass`` over ``nrows`` samples is launched with.
+
+    Wave ``w`` of ``W`` walks schedule positions ``w, w + W, w + 2W, ...``
+    sequentially (position ``p`` is sample ``perm[p]``, or ``p`` without a
+    permutation)."""
+    return int(_require_hip().sdca_num_waves(int(nrows)))
+
+
 def csr_row_norms_sq(csr: CSR) -> torch.Tensor:
     row_ids = torch.repeat_interleave(
         torch.arange(csr.num_rows, dtype=torch.int64, device=csr.device),

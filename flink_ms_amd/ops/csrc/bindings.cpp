@@ -42,6 +42,7 @@ int fma_sdca_pass(const int64_t* indptr, const int* indices,
                   const float* values, const float* y, const float* norms_sq,
                   const int* perm, float* alpha, float* v, int64_t nrows,
                   float scale, void* stream);
+long long fma_sdca_num_waves(long long nrows);
 int fma_svm_margins(const int64_t* indptr, const int* indices,
                     const float* values, const float* w, float* out,
                     int64_t nrows, void* stream);
@@ -541,12 +542,30 @@ void sdca_pass(torch::Tensor indptr, torch::Tensor indices,
         check_t(perm, torch::kInt32, "perm");
         p = perm.data_ptr<int>();
     }
+    // the kernel indexes all per-sample arrays by row id: sizes must agree
+    // before anything is launched
+    TORCH_CHECK(indptr.numel() >= 1, "indptr must have nrows + 1 elements");
+    const int64_t nrows = indptr.numel() - 1;
+    TORCH_CHECK(y.numel() == nrows, "y must have nrows elements");
+    TORCH_CHECK(norms_sq.numel() == nrows,
+                "norms_sq must have nrows elements");
+    TORCH_CHECK(alpha.numel() == nrows, "alpha must have nrows elements");
+    TORCH_CHECK(perm.numel() == 0 || perm.numel() == nrows,
+                "perm must be empty or have nrows elements");
+    TORCH_CHECK(indices.numel() == values.numel(),
+                "indices and values must have the same length");
     check_hip(fma_sdca_pass(indptr.data_ptr<int64_t>(),
                             indices.data_ptr<int>(), values.data_ptr<float>(),
                             y.data_ptr<float>(), norms_sq.data_ptr<float>(),
                             p, alpha.data_ptr<float>(), v.data_ptr<float>(),
-                            indptr.size(0) - 1, (float)scale, (void*)stream),
+                            nrows, (float)scale, (void*)stream),
               "sdca_pass");
+}
+
+// Waves one sdca_pass launch over nrows samples runs with (the stride of the
+// kernel's sample schedule); host-only, no GPU needed.
+int64_t sdca_num_waves(int64_t nrows) {
+    return (int64_t)fma_sdca_num_waves(nrows);
 }
 
 void svm_margins(torch::Tensor indptr, torch::Tensor indices,
@@ -557,6 +576,9 @@ void svm_margins(torch::Tensor indptr, torch::Tensor indices,
     check_t(values, torch::kFloat32, "values");
     check_t(w, torch::kFloat32, "w");
     check_t(out, torch::kFloat32, "out");
+    TORCH_CHECK(indptr.numel() >= 1, "indptr must have nrows + 1 elements");
+    TORCH_CHECK(out.numel() >= indptr.numel() - 1,
+                "out must have at least nrows elements");
     check_hip(fma_svm_margins(indptr.data_ptr<int64_t>(),
                               indices.data_ptr<int>(),
                               values.data_ptr<float>(), w.data_ptr<float>(),
@@ -572,7 +594,12 @@ void predict_dot(torch::Tensor U, torch::Tensor V, torch::Tensor u_idx,
     check_t(u_idx, torch::kInt64, "u_idx");
     check_t(i_idx, torch::kInt64, "i_idx");
     check_t(out, torch::kFloat32, "out");
+    TORCH_CHECK(U.dim() == 2 && V.dim() == 2, "U and V must be 2-D");
     TORCH_CHECK(U.size(1) == V.size(1), "rank mismatch");
+    TORCH_CHECK(i_idx.numel() == u_idx.numel(),
+                "u_idx and i_idx must have the same length");
+    TORCH_CHECK(out.numel() >= u_idx.numel(),
+                "out must have at least one element per query");
     check_hip(fma_predict_dot(bf16_ptr(U), bf16_ptr(V),
                               u_idx.data_ptr<int64_t>(),
                               i_idx.data_ptr<int64_t>(),
@@ -594,10 +621,17 @@ void sgd_update(torch::Tensor U, torch::Tensor V, torch::Tensor u_idx,
         check_t(err_out, torch::kFloat32, "err_out");
         ep = err_out.data_ptr<float>();
     }
+    const int64_t nq = u_idx.numel();
+    TORCH_CHECK(U.dim() == 2 && V.dim() == 2, "U and V must be 2-D");
+    TORCH_CHECK(U.size(1) == V.size(1), "rank mismatch");
+    TORCH_CHECK(i_idx.numel() == nq && r.numel() == nq,
+                "u_idx, i_idx and r must have the same length");
+    TORCH_CHECK(err_out.numel() == 0 || err_out.numel() >= nq,
+                "err_out must be empty or have one element per query");
     check_hip(fma_sgd_update(bf16_ptr_mut(U), bf16_ptr_mut(V),
                              u_idx.data_ptr<int64_t>(),
                              i_idx.data_ptr<int64_t>(), r.data_ptr<float>(),
-                             ep, u_idx.numel(), (int)U.size(1), (float)lr,
+                             ep, nq, (int)U.size(1), (float)lr,
                              (float)user_reg, (float)item_reg, (void*)stream),
               "sgd_update");
 }
@@ -692,6 +726,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("ldl_solve_wave_reg", &ldl_solve_wave_reg);
     m.def("ldl_solve_wave_reg", &ldl_solve_wave_reg_v);
     m.def("sdca_pass", &sdca_pass);
+    m.def("sdca_num_waves", &sdca_num_waves);
     m.def("svm_margins", &svm_margins);
     m.def("predict_dot", &predict_dot);
     m.def("sgd_update", &sgd_update);

@@ -39,7 +39,11 @@ DEV_INLINE float bf2f(unsigned short u) {
 DEV_INLINE unsigned short f2bf(float f) {
     union { float f; unsigned int i; } v;
     v.f = f;
-    // round-to-nearest-even (matches torch bfloat16 casts for finite values)
+    // NaN stays NaN (sign kept, quiet bit set): the rounding carry below
+    // would turn a NaN with low payload bits into inf or a signed zero
+    if ((v.i & 0x7fffffffu) > 0x7f800000u)
+        return (unsigned short)((v.i >> 16) | 0x0040u);
+    // round-to-nearest-even (matches torch bfloat16 casts; inf maps to inf)
     unsigned int r = v.i + 0x7fffu + ((v.i >> 16) & 1u);
     return (unsigned short)(r >> 16);
 }

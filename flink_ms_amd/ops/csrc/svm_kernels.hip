@@ -102,17 +102,28 @@ __global__ void k_svm_margins(const long long* __restrict__ indptr,
     }
 }
 
-extern "C" hipError_t fma_sdca_pass(
-    const long long* indptr, const int* indices, const float* values,
-    const float* y, const float* norms_sq, const int* perm, float* alpha,
-    float* v, long long nrows, float scale, hipStream_t stream) {
-    if (nrows <= 0) return hipErrorInvalidValue;
+// Launch heuristic of k_sdca_pass: the number of blocks (4 waves each).
+static unsigned sdca_grid(long long nrows) {
     // keep >=16 samples sequential per wave: full-width hogwild degenerates
     // to a synchronous full-batch step and stalls dual convergence
     long long waves = nrows / 16;
     if (waves < 4) waves = 4;
     if (waves > 8192) waves = 8192;
-    unsigned grid = (unsigned)((waves + 3) / 4);
+    return (unsigned)((waves + 3) / 4);
+}
+
+// Waves k_sdca_pass is launched with for nrows samples, i.e. the stride of
+// its sample schedule: wave w walks schedule positions w, w + W, w + 2W, ...
+extern "C" long long fma_sdca_num_waves(long long nrows) {
+    return nrows <= 0 ? 0 : (long long)sdca_grid(nrows) * 4;
+}
+
+extern "C" hipError_t fma_sdca_pass(
+    const long long* indptr, const int* indices, const float* values,
+    const float* y, const float* norms_sq, const int* perm, float* alpha,
+    float* v, long long nrows, float scale, hipStream_t stream) {
+    if (nrows <= 0) return hipErrorInvalidValue;
+    const unsigned grid = sdca_grid(nrows);
     k_sdca_pass<<<dim3(grid), dim3(256), 0, stream>>>(
         indptr, indices, values, y, norms_sq, perm, alpha, v, nrows, scale);
     return hipGetLastError();

@@ -3,7 +3,10 @@
 Every HIP kernel in ``flink_ms_amd/ops/csrc/`` has a reference here computing
 the same contract in plain fp32 torch.  These are (a) the numerics oracle for
 the GPU parity tests and (b) the CPU execution path (this framework's tests
-must run without a GPU).
+must run without a GPU).  The SVM and serving ops also have float64 oracles
+(``*_f64``): the fp32 inputs are exact in float64, so they give the true
+result of the contract, against which both the fp32 reference and the
+kernels are measured.
 
 Op contracts mirror the reference's hot loops:
 - K1 Gramian assembly: per entity u, ``A_u = sum_{i in R(u)} q_i q_i^T
@@ -129,7 +132,73 @@ def sdca_epoch_reference(
         dalpha = a_new - float(alpha[i])
         if dalpha != 0.0:
             alpha[i] = a_new
-            v[xi_idx] += (dalpha * yi * scale) * xi_val
+            # accumulate: a feature id repeated inside the row gets the SUM
+            # of its updates (v += c * x_i), as the kernel's atomics give it
+            v.index_add_(0, xi_idx, (dalpha * yi * scale) * xi_val)
+
+
+def sdca_sequential_f64(
+    csr: CSR,
+    y: torch.Tensor,
+    alpha: torch.Tensor,
+    v: torch.Tensor,
+    lamb: float,
+    n_global: int,
+    order=None,
+    stale_reads: bool = False,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Float64 oracle of one SDCA pass over an explicit sample order.
+
+    Same contract as :func:`sdca_epoch_reference`, every quantity in float64
+    (the fp32 inputs are exact in it), accumulate semantics for repeated
+    feature ids.  ``order`` is the sequence of sample ids to visit (default
+    ``0..num_rows-1``).  Inputs are left alone; returns ``(alpha, v)`` as new
+    float64 tensors.
+
+    ``stale_reads=True`` is the deliberately WRONG variant in which every
+    step computes its margin from the initial ``v`` (updates still
+    accumulate): what a solver that never sees its own earlier updates would
+    give.  Tests use it to show they can tell the two apart.
+    """
+    indptr = csr.indptr.tolist()
+    idx = csr.indices.long().cpu()
+    val = csr.values.to(torch.float64).cpu()
+    y64 = y.to(torch.float64).cpu()
+    a64 = alpha.to(torch.float64).cpu().clone()
+    v64 = v.to(torch.float64).cpu().clone()
+    v_read = v64.clone() if stale_reads else v64
+    if order is None:
+        order = range(csr.num_rows)
+    elif isinstance(order, torch.Tensor):
+        order = order.tolist()
+    scale = 1.0 / (lamb * n_global)
+    for i in order:
+        s, e = indptr[i], indptr[i + 1]
+        if s == e:
+            continue
+        xi_idx = idx[s:e]
+        xi_val = val[s:e]
+        norm_sq = float((xi_val * xi_val).sum())
+        if norm_sq == 0.0:
+            continue
+        yi = float(y64[i])
+        a_old = float(a64[i])
+        margin = yi * float((v_read[xi_idx] * xi_val).sum())
+        grad = (1.0 - margin) / (norm_sq * scale)
+        a_new = min(1.0, max(0.0, a_old + grad))
+        dalpha = a_new - a_old
+        if dalpha != 0.0:
+            a64[i] = a_new
+            v64.index_add_(0, xi_idx, (dalpha * yi * scale) * xi_val)
+    return a64, v64
+
+
+def svm_margins_f64(csr: CSR, w: torch.Tensor) -> torch.Tensor:
+    """Float64 oracle of the CSR decision values ``<w, x_i>``."""
+    return svm_margins_reference(
+        CSR(csr.indptr, csr.indices, csr.values.to(torch.float64),
+            csr.num_rows, csr.num_cols),
+        w.to(torch.float64))
 
 
 def svm_margins_reference(csr: CSR, w: torch.Tensor) -> torch.Tensor:
@@ -174,7 +243,35 @@ def sgd_update_reference(
     return p_new, q_new, err
 
 
+def sgd_update_f64(
+    p: torch.Tensor,
+    q: torch.Tensor,
+    r: torch.Tensor,
+    lr: float,
+    user_reg: float,
+    item_reg: float,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Float64 oracle of the v1 SGD update: ``(p_new, q_new, err)`` in
+    float64 from the gathered old rows (bf16/fp32 inputs are exact in it)."""
+    return sgd_update_reference(
+        p.to(torch.float64), q.to(torch.float64), r.to(torch.float64),
+        lr, user_reg, item_reg)
+
+
 # ---------------------------------------------------------------------- K5
+
+def predict_dot_f64(
+    user_factors: torch.Tensor,
+    item_factors: torch.Tensor,
+    u_idx: torch.Tensor,
+    i_idx: torch.Tensor,
+) -> torch.Tensor:
+    """Float64 oracle of the batched predictions ``dot(U[u], V[i])``."""
+    p = user_factors[u_idx.long()].to(torch.float64)
+    q = item_factors[i_idx.long()].to(torch.float64)
+    return (p * q).sum(dim=-1)
+
+
 
 def predict_dot_reference(
     user_factors: torch.Tensor,

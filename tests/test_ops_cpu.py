@@ -109,6 +109,84 @@ def test_sdca_reference_converges():
     assert (alpha >= 0).all() and (alpha <= 1).all()
 
 
+def test_sdca_reference_repeated_feature_accumulates():
+    """A feature id repeated inside a row must move v by the SUM of its
+    duplicate values (v += c * x_i), consistently with how the dot and
+    ||x||^2 count both entries."""
+    from flink_ms_amd.data.blocked import CSR
+    # one row: feature 2 appears twice (0.5 and 1.5), feature 0 once (1.0)
+    csr = CSR(torch.tensor([0, 3]), torch.tensor([2, 0, 2], dtype=torch.int32),
+              torch.tensor([0.5, 1.0, 1.5]), 1, 4)
+    y = torch.tensor([1.0])
+    # scale = 1/(lamb*n) = 2, ||x||^2 = 3.5, v = 0: grad = 1/7, dalpha = 1/7
+    lamb, n = 0.25, 2
+    c = (1.0 / 7.0) * 2.0
+    want = torch.tensor([c * 1.0, 0.0, c * (0.5 + 1.5), 0.0],
+                        dtype=torch.float64)
+    alpha, v = torch.zeros(1), torch.zeros(4)
+    R.sdca_epoch_reference(csr, y, alpha, v, lamb, n)
+    assert torch.allclose(alpha, torch.tensor([1.0 / 7.0]), rtol=1e-6)
+    assert torch.allclose(v.double(), want, rtol=1e-6), v
+    a64, v64 = R.sdca_sequential_f64(csr, y, torch.zeros(1), torch.zeros(4),
+                                     lamb, n)
+    assert a64.dtype == torch.float64 and v64.dtype == torch.float64
+    assert torch.allclose(v64, want, rtol=1e-12), v64
+    # a second visit reads both duplicates back through the dot
+    a64b, v64b = R.sdca_sequential_f64(csr, y, torch.zeros(1), torch.zeros(4),
+                                       lamb, n, order=[0, 0])
+    # <v, x> = c * (1 + 2*0.5 + 2*1.5) = 10/7: grad = (1 - 10/7) / 7 = -3/49,
+    # alpha = 1/7 - 3/49 = 4/49, and v scales with alpha
+    assert torch.allclose(a64b, torch.tensor([4.0 / 49.0],
+                                             dtype=torch.float64), rtol=1e-12)
+    assert torch.allclose(v64b, want * (4.0 / 7.0), rtol=1e-12)
+
+
+def test_fp32_references_agree_with_f64_oracles():
+    """The fp32 references land within fp32 rounding of the float64 oracles
+    (the yardstick the GPU tests scale their tolerances from)."""
+    from flink_ms_amd.data.libsvm import LibSVMShape, synthetic_libsvm
+    csr, y = synthetic_libsvm(LibSVMShape(120, 40, 9), seed=11)
+    g = torch.Generator().manual_seed(12)
+    # shared features, a random order, repeated ids (drawn with replacement)
+    perm = torch.randperm(120, generator=g)
+    alpha = torch.rand(120, generator=g)
+    v = torch.randn(40, generator=g) * 0.1
+    a64, v64 = R.sdca_sequential_f64(csr, y, alpha, v, 0.05, 200, order=perm)
+    a32, v32 = alpha.clone(), v.clone()
+    R.sdca_epoch_reference(csr, y, a32, v32, 0.05, 200, perm)
+    assert (a64 != alpha.double()).sum() > 60        # the pass did something
+    # 120 chained fp32 steps; each is a handful of roundings of O(1) values
+    assert (a32.double() - a64).abs().max() < 1e-5
+    assert (v32.double() - v64).abs().max() < 1e-5 * float(v64.abs().max())
+    # the stale-read variant is a different (wrong) algorithm
+    _, v_stale = R.sdca_sequential_f64(csr, y, alpha, v, 0.05, 200,
+                                       order=perm, stale_reads=True)
+    assert (v_stale - v64).abs().max() > 1e-2
+
+    w = torch.randn(40, generator=g)
+    m64 = R.svm_margins_f64(csr, w)
+    m32 = R.svm_margins_reference(csr, w)
+    assert m64.dtype == torch.float64
+    assert (m32.double() - m64).abs().max() < 1e-5
+
+    U = torch.randn(7, 10, generator=g).to(torch.bfloat16)
+    V = torch.randn(9, 10, generator=g).to(torch.bfloat16)
+    u = torch.tensor([0, 6, 6, 3])
+    i = torch.tensor([8, 0, 8, 8])
+    d64 = R.predict_dot_f64(U, V, u, i)
+    assert d64.dtype == torch.float64
+    assert torch.equal(d64[0], (U[0].double() * V[8].double()).sum())
+    assert (R.predict_dot_reference(U, V, u, i).double() - d64).abs().max() < 1e-5
+
+    p, q = U[u[:2]].float(), V[i[:2]].float()
+    r = torch.tensor([3.0, 1.5])
+    got = R.sgd_update_reference(p, q, r, 0.125, 0.03125, 0.0625)
+    want = R.sgd_update_f64(p, q, r, 0.125, 0.03125, 0.0625)
+    for a, b in zip(got, want):
+        assert b.dtype == torch.float64
+        assert (a.double() - b).abs().max() < 1e-5
+
+
 def test_csr_transpose_involution():
     from flink_ms_amd.data.blocked import csr_from_coo, csr_transpose
 
