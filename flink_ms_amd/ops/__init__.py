@@ -9,6 +9,7 @@ reference implementations (``flink_ms_amd.ops.reference``) run instead.
 
 from __future__ import annotations
 
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -100,13 +101,33 @@ def _wreg_broadcast() -> int:
     v_readlane broadcasts, branch-free substitutions), ``shfl`` (the LDS
     shuffle path), or the ladder steps ``panel`` / ``subst`` (wave-fused
     kernel only)."""
-    import os as _os
-    name = _os.environ.get("FMA_WREG_BROADCAST", "readlane")
+    name = os.environ.get("FMA_WREG_BROADCAST", "readlane")
     if name not in _WREG_BROADCAST:
         raise ValueError(
             f"FMA_WREG_BROADCAST={name!r}: expected one of "
             f"{sorted(_WREG_BROADCAST)}")
     return _WREG_BROADCAST[name]
+
+
+def _launch_fused(ops, indptr, csr: CSR, fac, out, ob, o8, ro, reg,
+                  block: bool, allow_db: bool = False) -> None:
+    """Launch the fused Gramian+solve kernel for ``fac``'s rank and dtype:
+    the wave-fused kernel for k <= 64, the block-fused kernel for k > 64 or
+    ``block=True``.  ``indptr`` bounds the launch (nrows = len - 1); ``ob``
+    / ``o8`` / ``ro`` are the optional bf16 / e4m3 images and launch
+    schedule (empty = absent).  The block kernel writes only the image of
+    the gather dtype."""
+    fp8 = fac.dtype == torch.uint8
+    args = (indptr, csr.indices, csr.values, fac, out)
+    if block or fac.shape[1] > 64:
+        none = _empty(fac.device)
+        ops.als_solve_fused(*args, none if fp8 else ob, o8 if fp8 else none,
+                            ro, float(reg), _stream())
+        return
+    fn = ops.als_solve_wavefused
+    if allow_db and fp8 and os.environ.get("FMA_WAVEFUSED_DB") == "1":
+        fn = ops.als_solve_wavefused_db
+    fn(*args, ob, o8, ro, float(reg), _stream(), _wreg_broadcast())
 
 
 def als_solve_side(
@@ -151,35 +172,16 @@ def als_solve_side(
         o8 = out_fp8 if out_fp8 is not None else _empty(fac.device)
         ro = row_order if row_order is not None else _empty(fac.device)
         korig = other_factors.shape[1]
-        if fused or k > 64:
-            # bf16 k>64 (and explicit fused=True): block-fused kernel (no
-            # nrows*k*k A round-trip through HBM)
-            out = torch.empty(csr.num_rows, k, dtype=torch.float32,
-                              device=fac.device)
-            if fp8:
-                ops.als_solve_fused_fp8(csr.indptr, csr.indices, csr.values,
-                                        fac, out, o8, ro, float(reg),
-                                        _stream())
-            else:
-                ops.als_solve_fused(csr.indptr, csr.indices, csr.values, fac,
-                                    out, ob, ro, float(reg), _stream())
-        elif slab_rows is None:
+        if fused or k > 64 or slab_rows is None:
+            # block-fused for k > 64 (and explicit fused=True), else the
             # k<=64 default: wave-fused Gramian+LDL — one wave per entity,
-            # A lives only in MFMA C-fragments (no nrows*k*k HBM round
-            # trip, no barriers; the r2 profile showed the modular path
-            # bound by exactly that A write+read traffic)
+            # A lives only in MFMA C-fragments.  Neither pays the modular
+            # path's nrows*k*k A round trip through HBM (the r2 profile
+            # showed that path bound by exactly that write+read traffic)
             out = torch.empty(csr.num_rows, k, dtype=torch.float32,
                               device=fac.device)
-            import os as _os
-            if fp8 and _os.environ.get("FMA_WAVEFUSED_DB") == "1":
-                ops.als_solve_wavefused_db(csr.indptr, csr.indices,
-                                           csr.values, fac, out, ob, o8,
-                                           ro, float(reg), _stream(),
-                                           _wreg_broadcast())
-            else:
-                ops.als_solve_wavefused(csr.indptr, csr.indices, csr.values,
-                                        fac, out, ob, o8, ro, float(reg),
-                                        _stream(), _wreg_broadcast())
+            _launch_fused(ops, csr.indptr, csr, fac, out, ob, o8, ro, reg,
+                          block=fused, allow_db=True)
         else:
             # slab the normal equations: A is nrows*k*k fp32, which at the
             # 1B-rating configs would exceed HBM if materialized whole.
@@ -205,9 +207,8 @@ def als_solve_side(
             for s in range(0, csr.num_rows, slab):
                 e = min(s + slab, csr.num_rows)
                 As, bs = A[: e - s], b[: e - s]
-                gram = ops.gramian_fp8 if fp8 else ops.gramian
-                gram(csr.indptr[s:e + 1], csr.indices, csr.values,
-                     fac, As, bs, use_ro, float(reg), _stream())
+                ops.gramian(csr.indptr[s:e + 1], csr.indices, csr.values,
+                            fac, As, bs, use_ro, float(reg), _stream())
                 obs = ob[s:e] if ob.numel() > 0 else ob
                 o8s = o8[s:e] if o8.numel() > 0 else o8
                 if k <= 64:
@@ -248,7 +249,6 @@ def als_solve_chunk(
         fp8 = other_factors.dtype == torch.uint8
         fac = (other_factors.contiguous() if fp8
                else other_factors.to(torch.bfloat16).contiguous())
-        k = fac.shape[1]
         ids = entity_ids.to(torch.int32).contiguous()
         sub_indptr = csr.indptr  # full: kernels index it via row_order
         o8 = out_fp8 if out_fp8 is not None else _empty(fac.device)
@@ -256,16 +256,8 @@ def als_solve_chunk(
         # row_order-driven launch needs indptr[0:nrows+1] only for bounds;
         # pass a view sized to the slab so nrows = len(ids)
         ip = sub_indptr[: ids.numel() + 1]
-        if k <= 64:
-            ops.als_solve_wavefused(ip, csr.indices, csr.values, fac,
-                                    out_f32, ob, o8, ids, float(reg),
-                                    _stream(), _wreg_broadcast())
-        elif fp8:
-            ops.als_solve_fused_fp8(ip, csr.indices, csr.values, fac,
-                                    out_f32, o8, ids, float(reg), _stream())
-        else:
-            ops.als_solve_fused(ip, csr.indices, csr.values, fac,
-                                out_f32, ob, ids, float(reg), _stream())
+        _launch_fused(ops, ip, csr, fac, out_f32, ob, o8, ids, reg,
+                      block=False)
         return
     # CPU (gloo tests): contiguous id range sliced out of the CSR
     a = int(entity_ids.min()) if entity_ids.numel() else 0
@@ -295,9 +287,8 @@ def gramian(csr: CSR, factors: torch.Tensor, reg: float) -> Tuple[torch.Tensor, 
         k = fac.shape[1]
         A = torch.empty(csr.num_rows, k, k, dtype=torch.float32, device=fac.device)
         b = torch.empty(csr.num_rows, k, dtype=torch.float32, device=fac.device)
-        fn = ops.gramian_fp8 if fp8 else ops.gramian
-        fn(csr.indptr, csr.indices, csr.values, fac, A, b,
-           _empty(fac.device), float(reg), _stream())
+        ops.gramian(csr.indptr, csr.indices, csr.values, fac, A, b,
+                    _empty(fac.device), float(reg), _stream())
         korig = factors.shape[1]
         if korig != k:
             return A[:, :korig, :korig], b[:, :korig]

@@ -61,7 +61,7 @@ def build(verbose: bool = True, force: bool = False) -> Path:
     srcs = [CSRC / s for s in KERNEL_SOURCES] + [CSRC / "bindings.cpp",
                                                  kv_src]
     deps = srcs + [CSRC / "common.hip.h", CSRC / "als_kernels_device.inc",
-            Path(__file__)]
+                   CSRC / "fma_api.h", Path(__file__)]
     if not force and SO_PATH.exists():
         so_mtime = SO_PATH.stat().st_mtime
         if all(d.stat().st_mtime < so_mtime for d in deps):

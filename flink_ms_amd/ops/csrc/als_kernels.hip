@@ -13,64 +13,87 @@
 //          an extra staged 16-column block as a bf16 hi/lo pair, so b falls
 //          out of the same MFMAs (columns 0/1 of the EXT tiles).
 //   K2  p_u = A_u^{-1} b_u
-//       -> in-LDS LDL^T factorization (register panels + f32-MFMA trailing
+//       -> LDL^T factorization (register panels + f32-MFMA trailing
 //          updates) and substitution solves: wave-per-entity for k <= 64
-//          (k_ldl_solve_wave, the modular default) or 256-thread blocks up
-//          to k = 128 (cholesky_lds/solve_lds_block, also fused with K1 in
-//          k_als_solve_fused so A never round-trips through HBM).
+//          (k_ldl_solve_wave_reg, A in MFMA C-fragments; fused with K1 in
+//          k_als_solve_wavefused) or 256-thread blocks up to k = 128
+//          (cholesky_lds_tri/solve_lds_block_tri over an LDS image, fused
+//          with K1 in k_als_solve_fused) -- fused, A never round-trips
+//          through HBM.
 //
-// Gramian geometry: one workgroup (256 threads = 4 waves) per entity;
+// Every Gramian kernel is templated on <KT, FP8>: factor rank k = 16*KT
+// (KT 1..8, wrappers pad) and the gather precision (bf16 words or e4m3
+// bytes); everything downstream of the MFMAs is fp32 either way.
+//
+// Block-path geometry: one workgroup (256 threads = 4 waves) per entity;
 // grid = #entities; wave w owns accumulator tiles t = w, w+4, ... of the
-// upper-triangle + EXT tile list.  Factor rank k = 16*KT, KT 1..8
-// (wrappers pad).
+// upper-triangle + EXT tile list.
 //
 // LDS layout per block (union; the stage dies before A is born):
-//   stage: TRANSPOSED Gt[K+16 rows][32 ratings] bf16, 96-B row stride
-//          (24 dwords: 16 used + 8 pad).  Rows 0..K-1 hold the gathered
-//          factor columns, rows K..K+1 the rating hi/lo pair, K+2..K+15
-//          zeros.  Each MFMA fragment is ONE bank-conflict-free
-//          ds_read_b128; staging transposes 4x4 bf16 blocks in registers
-//          (als_kernels_device.inc).
-//   A:     [K][K+1] fp32 (padded leading dim -> conflict-free column walks)
-//   b_hi/b_lo: [K] fp32 each, then a 16x16 pivot-column scratch.
+//   stage: TRANSPOSED Gt[K+16 rows][32 ratings], one buffer per chunk in
+//          flight.  bf16: 96-B row stride (24 dwords: 16 used + 8 pad),
+//          one ds_read_b128 per MFMA fragment; e4m3: 40-B stride, one
+//          ds_read_b64.  Rows 0..K-1 hold the gathered factor columns,
+//          rows K..K+1 the rating hi/lo pair, K+2..K+15 zeros; staging
+//          transposes in registers (als_kernels_device.inc).
+//   A:     solver image (k_als_solve_fused, k_cholesky_solve): the
+//          KT(KT+1)/2 lower-triangle 16x16 fp32 tiles, row stride 17
+//          (Geo::LDT; conflict-free column walks), then b_hi/b_lo and the
+//          substitution's x buffer, [K] fp32 each.
+//          k_gramian, which only exports A, keeps the square [K][K+1]
+//          image (write_acc mirrors the upper tiles into it).
+//
+// File layout: kernels first (block path, wave solvers, wave-fused,
+// wave-quad, MFMA probes), then every extern "C" launcher declared in
+// fma_api.h.
 
 #include "common.hip.h"
 
 #include "als_kernels_device.inc"
+#include "fma_api.h"
 
 // -------------------------------------------------------------- kernels
 
-// Fused K1+K2: normal equations + Cholesky solve, one entity per block.
-template <int KT>
+// Fused K1+K2: normal equations + LDL^T solve, one entity per block.
+// FP8 selects the gather precision and, with it, the low-precision image of
+// the solution written beside out_f32 for the next half-iteration (bf16
+// words or e4m3 bytes; out_lowp may be null).
+template <int KT, bool FP8>
 __launch_bounds__(256)
 // waves_per_eu(3): without it the allocator splits 93 VGPR + 88 AGPR
 // (181 total -> 2 waves/SIMD); constrained it finds a 127-VGPR, zero-AGPR,
 // zero-spill allocation -> 3-4 waves/SIMD (measured: the K=128 fused
 // kernel is the whole 1B-config iteration)
 __attribute__((amdgpu_waves_per_eu(3)))
-__global__ void k_als_solve_fused(const long long* __restrict__ indptr,
-                                  const int* __restrict__ indices,
-                                  const float* __restrict__ values,
-                                  const unsigned short* __restrict__ factors,
-                                  float* __restrict__ out_f32,
-                                  unsigned short* __restrict__ out_bf16,
-                                  const int* __restrict__ row_order,
-                                  long long nrows, float reg) {
+__global__ void k_als_solve_fused(
+    const long long* __restrict__ indptr, const int* __restrict__ indices,
+    const float* __restrict__ values,
+    const typename GatherT<FP8>::elem* __restrict__ factors,
+    float* __restrict__ out_f32,
+    typename GatherT<FP8>::elem* __restrict__ out_lowp,
+    const int* __restrict__ row_order, long long nrows, float reg) {
     constexpr int K = Geo<KT>::K;
-    __shared__ __align__(16) char smem[Geo<KT>::SMEM_TRI];
+    __shared__ __align__(16) char
+        smem[FP8 ? Geo<KT>::SMEM8_TRI : Geo<KT>::SMEM_TRI];
     long long row = blockIdx.x;
     if (row >= nrows) return;
     if (row_order) row = row_order[row];
 
-    const int n = gramian_to_lds<KT, true, true>(smem, indptr, indices,
-                                                 values, factors, row, reg);
-    if (n == 0) { write_zero_row<KT>(out_f32, out_bf16, row); return; }
+    const int n = gramian_to_lds<KT, true, true, FP8>(
+        smem, indptr, indices, values, factors, row, reg);
+    if (n == 0) { write_zero_row<KT>(out_f32, out_lowp, row); return; }
 
     float* A = (float*)smem;
     float* b = A + Geo<KT>::A_TRI_FLOATS;
-    cholesky_lds_tri<K>(A, b + 2 * K);
-    solve_lds_block_tri<K>(A, b, b + 2 * K, out_f32 + row * K,
-                           out_bf16 ? out_bf16 + row * K : nullptr);
+    cholesky_lds_tri<K>(A);
+    // the solver takes one pointer per image format (k_cholesky_solve
+    // passes neither); each instantiation here hands it exactly one
+    if constexpr (FP8)
+        solve_lds_block_tri<K>(A, b, b + 2 * K, out_f32 + row * K, nullptr,
+                               out_lowp ? out_lowp + row * K : nullptr);
+    else
+        solve_lds_block_tri<K>(A, b, b + 2 * K, out_f32 + row * K,
+                               out_lowp ? out_lowp + row * K : nullptr);
 }
 
 // Standalone K1 (for parity tests / modular path): writes dense A and b.
@@ -78,97 +101,23 @@ __global__ void k_als_solve_fused(const long long* __restrict__ indptr,
 // processes entity row_order[i] and writes A_out/b_out at THAT row, so the
 // downstream batched solve stays order-agnostic (heavy entities launch
 // first; avoids tail stragglers at the end of the grid).
-template <int KT>
+template <int KT, bool FP8>
 __launch_bounds__(256)
-__global__ void k_gramian(const long long* __restrict__ indptr,
-                          const int* __restrict__ indices,
-                          const float* __restrict__ values,
-                          const unsigned short* __restrict__ factors,
-                          float* __restrict__ A_out,   // [nrows][K][K]
-                          float* __restrict__ b_out,   // [nrows][K]
-                          const int* __restrict__ row_order,
-                          long long nrows, float reg) {
+__global__ void k_gramian(
+    const long long* __restrict__ indptr, const int* __restrict__ indices,
+    const float* __restrict__ values,
+    const typename GatherT<FP8>::elem* __restrict__ factors,
+    float* __restrict__ A_out,   // [nrows][K][K]
+    float* __restrict__ b_out,   // [nrows][K]
+    const int* __restrict__ row_order, long long nrows, float reg) {
     constexpr int K = Geo<KT>::K;
-    __shared__ __align__(16) char smem[Geo<KT>::SMEM];
+    __shared__ __align__(16) char smem[FP8 ? Geo<KT>::SMEM8 : Geo<KT>::SMEM];
     long long row = blockIdx.x;
     if (row >= nrows) return;
     if (row_order) row = row_order[row];
     const int tid = threadIdx.x;
 
-    const int n = gramian_to_lds<KT>(smem, indptr, indices, values, factors,
-                                     row, reg);
-    float* A = (float*)smem;
-    float* b = A + K * (K + 1);
-    if (n == 0) {
-        for (int i = tid; i < K * K; i += 256) A_out[row * K * K + i] = 0.0f;
-        for (int c = tid; c < K; c += 256) b_out[row * K + c] = 0.0f;
-        return;
-    }
-    for (int i = tid; i < K * K; i += 256)
-        A_out[row * K * K + i] = A[(i / K) * (K + 1) + (i % K)];
-    for (int c = tid; c < K; c += 256) b_out[row * K + c] = b[c];
-}
-
-// fp8 twins of the fused and standalone-K1 kernels: e4m3 factor gathers
-// (one cache line per k<=64 row) through gramian_to_lds_fp8; everything
-// downstream (fp32 A/b, LDL solve) is identical.  out_fp8 writes the next
-// half-iteration's e4m3 factor image alongside fp32 (and optional bf16).
-template <int KT>
-__launch_bounds__(256)
-// waves_per_eu(3): without it the allocator splits 93 VGPR + 88 AGPR
-// (181 total -> 2 waves/SIMD); constrained it finds a 127-VGPR, zero-AGPR,
-// zero-spill allocation -> 3-4 waves/SIMD (measured: the K=128 fused
-// kernel is the whole 1B-config iteration)
-__attribute__((amdgpu_waves_per_eu(3)))
-__global__ void k_als_solve_fused_fp8(const long long* __restrict__ indptr,
-                                      const int* __restrict__ indices,
-                                      const float* __restrict__ values,
-                                      const unsigned char* __restrict__ factors,
-                                      float* __restrict__ out_f32,
-                                      unsigned char* __restrict__ out_fp8,
-                                      const int* __restrict__ row_order,
-                                      long long nrows, float reg) {
-    constexpr int K = Geo<KT>::K;
-    __shared__ __align__(16) char smem[Geo<KT>::SMEM8_TRI];
-    long long row = blockIdx.x;
-    if (row >= nrows) return;
-    if (row_order) row = row_order[row];
-
-    const int n = gramian_to_lds<KT, true, true, true>(smem, indptr,
-                                                       indices, values,
-                                                       factors, row, reg);
-    if (n == 0) {
-        for (int c = threadIdx.x; c < K; c += 256) {
-            out_f32[row * K + c] = 0.0f;
-            if (out_fp8) out_fp8[row * K + c] = 0;
-        }
-        return;
-    }
-    float* A = (float*)smem;
-    float* b = A + Geo<KT>::A_TRI_FLOATS;
-    cholesky_lds_tri<K>(A, b + 2 * K);
-    solve_lds_block_tri<K>(A, b, b + 2 * K, out_f32 + row * K, nullptr,
-                           out_fp8 ? out_fp8 + row * K : nullptr);
-}
-
-template <int KT>
-__launch_bounds__(256)
-__global__ void k_gramian_fp8(const long long* __restrict__ indptr,
-                              const int* __restrict__ indices,
-                              const float* __restrict__ values,
-                              const unsigned char* __restrict__ factors,
-                              float* __restrict__ A_out,   // [nrows][K][K]
-                              float* __restrict__ b_out,   // [nrows][K]
-                              const int* __restrict__ row_order,
-                              long long nrows, float reg) {
-    constexpr int K = Geo<KT>::K;
-    __shared__ __align__(16) char smem[Geo<KT>::SMEM8];
-    long long row = blockIdx.x;
-    if (row >= nrows) return;
-    if (row_order) row = row_order[row];
-    const int tid = threadIdx.x;
-
-    const int n = gramian_to_lds<KT, true, false, true>(
+    const int n = gramian_to_lds<KT, true, false, FP8>(
         smem, indptr, indices, values, factors, row, reg);
     float* A = (float*)smem;
     float* b = A + K * (K + 1);
@@ -211,163 +160,13 @@ __global__ void k_cholesky_solve(const float* __restrict__ A_in,  // [n][K][K]
     }
     for (int c = tid; c < K; c += 256) b[c] = b_in[row * K + c];
     __syncthreads();
-    if (phases & 1) cholesky_lds_tri<K>(A, b + 2 * K);
+    if (phases & 1) cholesky_lds_tri<K>(A);
     if (phases & 2) {
         solve_lds_block_tri<K>(A, b, b + 2 * K, x_out + row * K, nullptr);
     } else if (tid < K) {
         x_out[row * K + tid] = b[tid];
     }
 }
-
-// ------------------------------------------------------------- MFMA probes
-// Layout-validation kernels for tests/test_gpu_mfma.py.
-
-// f32 16x16x4 probe with the guide-documented operand maps
-// (cdna_hip_programming.md §3): definitive C/D-layout check.
-__global__ void k_mfma_probe_f32(const float* __restrict__ Amat,  // [16][4]
-                                 const float* __restrict__ Bmat,  // [4][16]
-                                 float* __restrict__ D) {         // [16][16]
-    const int lane = threadIdx.x;
-    const float a = Amat[(lane & 15) * 4 + (lane >> 4)];
-    const float b = Bmat[(lane >> 4) * 16 + (lane & 15)];
-    f32x4 acc{0, 0, 0, 0};
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-        D[((lane >> 4) * 4 + r) * 16 + (lane & 15)] = acc[r];
-}
-
-// bf16 16x16x32 probe through the exact stage/frag machinery of the Gramian:
-// C[16][16] = Xt^T @ Yt for Xt, Yt [32][16] bf16.
-__global__ void k_mfma_probe_bf16(const unsigned short* __restrict__ Xt,
-                                  const unsigned short* __restrict__ Yt,
-                                  float* __restrict__ C) {
-    auto stage_xor = [](int row) -> unsigned { return (row & 8) ? 32u : 0u; };
-    constexpr int SP = 32;  // 2 tiles of 16 cols; SP*2 = 64B, XOR-closed
-    __shared__ __align__(16) unsigned short st[32 * SP];
-    const int lane = threadIdx.x;  // launched with 64 threads
-    {
-        const int row = lane & 31, tile = lane >> 5;
-        const unsigned short* src = (tile == 0 ? Xt : Yt) + row * 16;
-        for (int h = 0; h < 2; ++h) {
-            unsigned byte = (unsigned)(row * SP + tile * 16 + h * 8) * 2u
-                            ^ stage_xor(row);
-            *(uint4*)((char*)st + byte) = *(const uint4*)(src + h * 8);
-        }
-    }
-    __syncthreads();
-    const int g = lane >> 4, li = lane & 15;
-    const unsigned xorb = (g & 1) ? 32u : 0u;
-    bf16x8 frag[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        bf16x8 f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            unsigned byte = (unsigned)((8 * g + j) * SP + t * 16 + li) * 2u;
-            f[j] = *(const short*)((const char*)st + (byte ^ xorb));
-        }
-        frag[t] = f;
-    }
-    f32x4 acc{0, 0, 0, 0};
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag[0], frag[1], acc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-        C[(g * 4 + r) * 16 + li] = acc[r];
-}
-
-// fp8 e4m3 16x16x32 probe through the fp8 stage geometry (TROW8 rows,
-// ds_read_b64 fragments): C[16][16] = Xt^T @ Yt for Xt, Yt [32][16] e4m3
-// bytes.  Validates the (lane, element) map + C/D layout assumption of
-// k_gramian_fp8 against a torch reference (tests/test_gpu_mfma.py).
-__global__ void k_mfma_probe_fp8(const unsigned char* __restrict__ Xt,
-                                 const unsigned char* __restrict__ Yt,
-                                 float* __restrict__ C) {
-    constexpr int TROW8 = 40;
-    __shared__ __align__(8) char st[32 * TROW8];
-    const int lane = threadIdx.x;  // launched with 64 threads
-    for (int i = lane; i < 2 * 16 * 32; i += 64) {
-        const int tile = i >> 9, rem = i & 511;
-        const int r = rem >> 4, c = rem & 15;   // rating r, column c
-        st[(tile * 16 + c) * TROW8 + r] = (tile == 0 ? Xt : Yt)[r * 16 + c];
-    }
-    __syncthreads();
-    const int g = lane >> 4, li = lane & 15;
-    const fp8x8 fx = *(const fp8x8*)(st + (li)*TROW8 + g * 8);
-    const fp8x8 fy = *(const fp8x8*)(st + (16 + li) * TROW8 + g * 8);
-    f32x4 acc{0, 0, 0, 0};
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(fx, fy, acc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-        C[(g * 4 + r) * 16 + li] = acc[r];
-}
-
-// -------------------------------------------------------------- launchers
-
-extern "C" hipError_t fma_als_solve_fused(
-    int k, const long long* indptr, const int* indices, const float* values,
-    const unsigned short* factors, float* out_f32, unsigned short* out_bf16,
-    const int* row_order, long long nrows, float reg, hipStream_t stream) {
-    if (k % 16 || k < 16 || k > 128 || nrows <= 0) return hipErrorInvalidValue;
-    dim3 grid((unsigned)nrows), block(256);
-    DISPATCH_KT(k, (k_als_solve_fused<KT><<<grid, block, 0, stream>>>(
-        indptr, indices, values, factors, out_f32, out_bf16, row_order,
-        nrows, reg)));
-    return hipGetLastError();
-}
-
-extern "C" hipError_t fma_gramian(
-    int k, const long long* indptr, const int* indices, const float* values,
-    const unsigned short* factors, float* A_out, float* b_out,
-    const int* row_order, long long nrows, float reg, hipStream_t stream) {
-    if (k % 16 || k < 16 || k > 128 || nrows <= 0) return hipErrorInvalidValue;
-    dim3 grid((unsigned)nrows), block(256);
-    DISPATCH_KT(k, (k_gramian<KT><<<grid, block, 0, stream>>>(
-        indptr, indices, values, factors, A_out, b_out, row_order, nrows,
-        reg)));
-    return hipGetLastError();
-}
-
-extern "C" hipError_t fma_gramian_fp8(
-    int k, const long long* indptr, const int* indices, const float* values,
-    const unsigned char* factors, float* A_out, float* b_out,
-    const int* row_order, long long nrows, float reg, hipStream_t stream) {
-    if (k % 16 || k < 16 || k > 128 || nrows <= 0) return hipErrorInvalidValue;
-    dim3 grid((unsigned)nrows), block(256);
-    DISPATCH_KT(k, (k_gramian_fp8<KT><<<grid, block, 0, stream>>>(
-        indptr, indices, values, factors, A_out, b_out, row_order, nrows,
-        reg)));
-    return hipGetLastError();
-}
-
-extern "C" hipError_t fma_als_solve_fused_fp8(
-    int k, const long long* indptr, const int* indices, const float* values,
-    const unsigned char* factors, float* out_f32, unsigned char* out_fp8,
-    const int* row_order, long long nrows, float reg, hipStream_t stream) {
-    if (k % 16 || k < 16 || k > 128 || nrows <= 0) return hipErrorInvalidValue;
-    dim3 grid((unsigned)nrows), block(256);
-    DISPATCH_KT(k, (k_als_solve_fused_fp8<KT><<<grid, block, 0, stream>>>(
-        indptr, indices, values, factors, out_f32, out_fp8, row_order,
-        nrows, reg)));
-    return hipGetLastError();
-}
-
-extern "C" hipError_t fma_cholesky_solve_ph(
-    int k, const float* A_in, const float* b_in, float* x_out,
-    long long nrows, int phases, hipStream_t stream) {
-    if (k % 16 || k < 16 || k > 128 || nrows <= 0) return hipErrorInvalidValue;
-    dim3 grid((unsigned)nrows), block(256);
-    DISPATCH_KT(k, (k_cholesky_solve<KT><<<grid, block, 0, stream>>>(
-        A_in, b_in, x_out, nrows, phases)));
-    return hipGetLastError();
-}
-
-extern "C" hipError_t fma_cholesky_solve(
-    int k, const float* A_in, const float* b_in, float* x_out,
-    long long nrows, hipStream_t stream) {
-    return fma_cholesky_solve_ph(k, A_in, b_in, x_out, nrows, 3, stream);
-}
-
 
 // -------- wave-per-entity LDL solver (k <= 64) --------
 // The block-per-entity factorization is issue-bound: ~100 instructions of
@@ -849,37 +648,6 @@ __global__ void k_ldl_solve_wave_reg(const float* __restrict__ A_in,
     }
 }
 
-extern "C" hipError_t fma_ldl_solve_wave_reg(
-    int k, const float* A_in, const float* b_in, float* x_out,
-    unsigned short* x_bf16, unsigned char* x_fp8, long long nrows,
-    int variant, hipStream_t stream) {
-    if (k % 16 || k < 16 || k > 64 || nrows <= 0) return hipErrorInvalidValue;
-    // the intermediate ladder levels exist for k_als_solve_wavefused only
-    if (variant != WREG_BC_SHFL && variant != WREG_BC_HOIST)
-        return hipErrorInvalidValue;
-    dim3 grid((unsigned)((nrows + 3) / 4)), block(256);
-#define WR_CASE(KT)                                                           \
-    case KT:                                                                  \
-        if (variant == WREG_BC_SHFL)                                          \
-            k_ldl_solve_wave_reg<KT, WREG_BC_SHFL><<<grid, block, 0,          \
-                                                     stream>>>(               \
-                A_in, b_in, x_out, x_bf16, x_fp8, nrows);                     \
-        else                                                                  \
-            k_ldl_solve_wave_reg<KT, WREG_BC_HOIST><<<grid, block, 0,         \
-                                                      stream>>>(              \
-                A_in, b_in, x_out, x_bf16, x_fp8, nrows);                     \
-        break;
-    switch (k / 16) {
-        WR_CASE(1)
-        WR_CASE(2)
-        WR_CASE(3)
-        WR_CASE(4)
-        default: return hipErrorInvalidValue;
-    }
-#undef WR_CASE
-    return hipGetLastError();
-}
-
 // -------- wave-fused ALS solve (k <= 64): Gramian + LDL in ONE wave --------
 // r2 profiling: with the v2 multi-chunk gramian the modular path became
 // A-round-trip bound — the gramian writes nrows*K*K fp32 to HBM (~2.9 TB/s)
@@ -1115,39 +883,6 @@ __global__ void k_als_solve_wavefused_db(const long long* __restrict__ indptr,
     }
 }
 
-extern "C" hipError_t fma_als_solve_wavefused_db(
-    int k, const long long* indptr, const int* indices, const float* values,
-    const void* factors, float* out_f32, unsigned short* out_bf16,
-    unsigned char* out_fp8, const int* row_order, long long nrows,
-    float reg, int variant, hipStream_t stream) {
-    if (k % 16 || k < 16 || k > 64 || nrows <= 0) return hipErrorInvalidValue;
-    if (variant != WREG_BC_SHFL && variant != WREG_BC_HOIST)
-        return hipErrorInvalidValue;
-    dim3 grid((unsigned)((nrows + 3) / 4)), block(256);
-#define DB_CASE(KT)                                                           \
-    case KT:                                                                  \
-        if (variant == WREG_BC_SHFL)                                          \
-            k_als_solve_wavefused_db<KT, WREG_BC_SHFL><<<grid, block, 0,      \
-                                                         stream>>>(           \
-                indptr, indices, values, factors, out_f32, out_bf16,          \
-                out_fp8, row_order, nrows, reg);                              \
-        else                                                                  \
-            k_als_solve_wavefused_db<KT, WREG_BC_HOIST><<<grid, block, 0,     \
-                                                          stream>>>(          \
-                indptr, indices, values, factors, out_f32, out_bf16,          \
-                out_fp8, row_order, nrows, reg);                              \
-        break;
-    switch (k / 16) {
-        DB_CASE(1)
-        DB_CASE(2)
-        DB_CASE(3)
-        DB_CASE(4)
-        default: return hipErrorInvalidValue;
-    }
-#undef DB_CASE
-    return hipGetLastError();
-}
-
 template <int KT, bool FP8, int BC>
 __launch_bounds__(256)
 // waves_per_eu(5): 96 VGPRs with ~12-17 spilled (52-60 B/lane scratch) buys
@@ -1263,87 +998,6 @@ __global__ void k_als_solve_wavefused(const long long* __restrict__ indptr,
         if (out_bf16) out_bf16[e * K + lane] = f2bf(x0);
         if (out_fp8) out_fp8[e * K + lane] = f2fp8(x0);
     }
-}
-
-extern "C" hipError_t fma_als_solve_wavefused(
-    int k, int fp8, const long long* indptr, const int* indices,
-    const float* values, const void* factors, float* out_f32,
-    unsigned short* out_bf16, unsigned char* out_fp8, const int* row_order,
-    long long nrows, float reg, int variant, hipStream_t stream) {
-    if (k % 16 || k < 16 || k > 64 || nrows <= 0) return hipErrorInvalidValue;
-    dim3 grid((unsigned)((nrows + 3) / 4)), block(256);
-#define WF_LAUNCH(KT, BC)                                                     \
-    do {                                                                      \
-        if (fp8)                                                              \
-            k_als_solve_wavefused<KT, true, BC><<<grid, block, 0, stream>>>(  \
-                indptr, indices, values, factors, out_f32, out_bf16,          \
-                out_fp8, row_order, nrows, reg);                              \
-        else                                                                  \
-            k_als_solve_wavefused<KT, false, BC><<<grid, block, 0,            \
-                                                   stream>>>(                 \
-                indptr, indices, values, factors, out_f32, out_bf16,          \
-                out_fp8, row_order, nrows, reg);                              \
-    } while (0)
-#define WF_CASE(KT)                                                           \
-    case KT:                                                                  \
-        switch (variant) {                                                    \
-            case WREG_BC_SHFL: WF_LAUNCH(KT, WREG_BC_SHFL); break;            \
-            case WREG_BC_PANEL: WF_LAUNCH(KT, WREG_BC_PANEL); break;          \
-            case WREG_BC_SUBST: WF_LAUNCH(KT, WREG_BC_SUBST); break;          \
-            case WREG_BC_HOIST: WF_LAUNCH(KT, WREG_BC_HOIST); break;          \
-            default: return hipErrorInvalidValue;                             \
-        }                                                                     \
-        break;
-    switch (k / 16) {
-        WF_CASE(1)
-        WF_CASE(2)
-        WF_CASE(3)
-        WF_CASE(4)
-        default: return hipErrorInvalidValue;
-    }
-#undef WF_CASE
-#undef WF_LAUNCH
-    return hipGetLastError();
-}
-
-extern "C" hipError_t fma_ldl_solve_wave(
-    int k, const float* A_in, const float* b_in, float* x_out,
-    unsigned short* x_bf16, unsigned char* x_fp8, long long nrows,
-    hipStream_t stream) {
-    if (k % 16 || k < 16 || k > 64 || nrows <= 0) return hipErrorInvalidValue;
-    dim3 grid((unsigned)((nrows + 3) / 4)), block(256);
-    switch (k / 16) {
-        case 1: k_ldl_solve_wave<1><<<grid, block, 0, stream>>>(A_in, b_in, x_out, x_bf16, x_fp8, nrows); break;
-        case 2: k_ldl_solve_wave<2><<<grid, block, 0, stream>>>(A_in, b_in, x_out, x_bf16, x_fp8, nrows); break;
-        case 3: k_ldl_solve_wave<3><<<grid, block, 0, stream>>>(A_in, b_in, x_out, x_bf16, x_fp8, nrows); break;
-        case 4: k_ldl_solve_wave<4><<<grid, block, 0, stream>>>(A_in, b_in, x_out, x_bf16, x_fp8, nrows); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-extern "C" hipError_t fma_mfma_probe_f32(const float* A, const float* B,
-                                         float* D, hipStream_t stream) {
-    k_mfma_probe_f32<<<dim3(1), dim3(64), 0, stream>>>(A, B, D);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t fma_mfma_probe_bf16(const unsigned short* Xt,
-                                          const unsigned short* Yt, float* C,
-                                          hipStream_t stream) {
-    k_mfma_probe_bf16<<<dim3(1), dim3(64), 0, stream>>>(Xt, Yt, C);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t fma_mfma_probe_fp8(const unsigned char* Xt,
-                                         const unsigned char* Yt, float* C,
-                                         hipStream_t stream) {
-    k_mfma_probe_fp8<<<dim3(1), dim3(64), 0, stream>>>(Xt, Yt, C);
-    return hipGetLastError();
-}
-
-extern "C" const char* fma_err_str(int err) {
-    return hipGetErrorString((hipError_t)err);
 }
 
 // ------- wave-QUAD fused ALS solve (64 < k <= 128, fp8 gathers) -------
@@ -1735,19 +1389,282 @@ __global__ void k_als_solve_wavefused2(const long long* __restrict__ indptr,
     }
 }
 
-extern "C" hipError_t fma_als_solve_wavefused2(
+// ------------------------------------------------------------- MFMA probes
+// Layout-validation kernels for tests/test_gpu_mfma.py.
+
+// f32 16x16x4 probe with the guide-documented operand maps
+// (cdna_hip_programming.md §3): definitive C/D-layout check.
+__global__ void k_mfma_probe_f32(const float* __restrict__ Amat,  // [16][4]
+                                 const float* __restrict__ Bmat,  // [4][16]
+                                 float* __restrict__ D) {         // [16][16]
+    const int lane = threadIdx.x;
+    const float a = Amat[(lane & 15) * 4 + (lane >> 4)];
+    const float b = Bmat[(lane >> 4) * 16 + (lane & 15)];
+    f32x4 acc{0, 0, 0, 0};
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        D[((lane >> 4) * 4 + r) * 16 + (lane & 15)] = acc[r];
+}
+
+// bf16 16x16x32 probe through the exact stage/frag machinery of the Gramian:
+// C[16][16] = Xt^T @ Yt for Xt, Yt [32][16] bf16.
+__global__ void k_mfma_probe_bf16(const unsigned short* __restrict__ Xt,
+                                  const unsigned short* __restrict__ Yt,
+                                  float* __restrict__ C) {
+    auto stage_xor = [](int row) -> unsigned { return (row & 8) ? 32u : 0u; };
+    constexpr int SP = 32;  // 2 tiles of 16 cols; SP*2 = 64B, XOR-closed
+    __shared__ __align__(16) unsigned short st[32 * SP];
+    const int lane = threadIdx.x;  // launched with 64 threads
+    {
+        const int row = lane & 31, tile = lane >> 5;
+        const unsigned short* src = (tile == 0 ? Xt : Yt) + row * 16;
+        for (int h = 0; h < 2; ++h) {
+            unsigned byte = (unsigned)(row * SP + tile * 16 + h * 8) * 2u
+                            ^ stage_xor(row);
+            *(uint4*)((char*)st + byte) = *(const uint4*)(src + h * 8);
+        }
+    }
+    __syncthreads();
+    const int g = lane >> 4, li = lane & 15;
+    const unsigned xorb = (g & 1) ? 32u : 0u;
+    bf16x8 frag[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        bf16x8 f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            unsigned byte = (unsigned)((8 * g + j) * SP + t * 16 + li) * 2u;
+            f[j] = *(const short*)((const char*)st + (byte ^ xorb));
+        }
+        frag[t] = f;
+    }
+    f32x4 acc{0, 0, 0, 0};
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag[0], frag[1], acc, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        C[(g * 4 + r) * 16 + li] = acc[r];
+}
+
+// fp8 e4m3 16x16x32 probe through the fp8 stage geometry (TROW8 rows,
+// ds_read_b64 fragments): C[16][16] = Xt^T @ Yt for Xt, Yt [32][16] e4m3
+// bytes.  Validates the (lane, element) map + C/D layout assumption of
+// k_gramian<KT, true> against a torch reference (tests/test_gpu_mfma.py).
+__global__ void k_mfma_probe_fp8(const unsigned char* __restrict__ Xt,
+                                 const unsigned char* __restrict__ Yt,
+                                 float* __restrict__ C) {
+    constexpr int TROW8 = 40;
+    __shared__ __align__(8) char st[32 * TROW8];
+    const int lane = threadIdx.x;  // launched with 64 threads
+    for (int i = lane; i < 2 * 16 * 32; i += 64) {
+        const int tile = i >> 9, rem = i & 511;
+        const int r = rem >> 4, c = rem & 15;   // rating r, column c
+        st[(tile * 16 + c) * TROW8 + r] = (tile == 0 ? Xt : Yt)[r * 16 + c];
+    }
+    __syncthreads();
+    const int g = lane >> 4, li = lane & 15;
+    const fp8x8 fx = *(const fp8x8*)(st + (li)*TROW8 + g * 8);
+    const fp8x8 fy = *(const fp8x8*)(st + (16 + li) * TROW8 + g * 8);
+    f32x4 acc{0, 0, 0, 0};
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(fx, fy, acc, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        C[(g * 4 + r) * 16 + li] = acc[r];
+}
+
+// -------------------------------------------------------------- launchers
+// The definitions of fma_api.h's ALS entry points.  Each checks k and
+// nrows, picks the instantiation through dispatch_ic (k/16, then the gather
+// precision or the broadcast variant where the kernel has one) and returns
+// the launch status.
+
+namespace {
+
+const dim3 kBlock(256);
+// one entity per block / four entities (one per wave) per block
+inline dim3 grid_block(long long nrows) { return dim3((unsigned)nrows); }
+inline dim3 grid_wave(long long nrows) {
+    return dim3((unsigned)((nrows + 3) / 4));
+}
+inline bool bad_shape(int k, long long nrows) {
+    return k % 16 != 0 || nrows <= 0;
+}
+
+}  // namespace
+
+extern "C" const char* fma_err_str(int err) {
+    return hipGetErrorString((hipError_t)err);
+}
+
+extern "C" int fma_als_solve_fused(
+    int k, int fp8, const long long* indptr, const int* indices,
+    const float* values, const void* factors, float* out_f32,
+    unsigned short* out_bf16, unsigned char* out_fp8, const int* row_order,
+    long long nrows, float reg, void* stream) {
+    if (bad_shape(k, nrows) || (fp8 ? out_bf16 != nullptr : out_fp8 != nullptr))
+        return hipErrorInvalidValue;
+    return dispatch_ic<1, 2, 3, 4, 5, 6, 7, 8>(k / 16, [&](auto kt) {
+        constexpr int KT = decltype(kt)::value;
+        if (fp8)
+            k_als_solve_fused<KT, true>
+                <<<grid_block(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                    indptr, indices, values, (const unsigned char*)factors,
+                    out_f32, out_fp8, row_order, nrows, reg);
+        else
+            k_als_solve_fused<KT, false>
+                <<<grid_block(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                    indptr, indices, values, (const unsigned short*)factors,
+                    out_f32, out_bf16, row_order, nrows, reg);
+        return hipGetLastError();
+    });
+}
+
+extern "C" int fma_gramian(
+    int k, int fp8, const long long* indptr, const int* indices,
+    const float* values, const void* factors, float* A_out, float* b_out,
+    const int* row_order, long long nrows, float reg, void* stream) {
+    if (bad_shape(k, nrows)) return hipErrorInvalidValue;
+    return dispatch_ic<1, 2, 3, 4, 5, 6, 7, 8>(k / 16, [&](auto kt) {
+        constexpr int KT = decltype(kt)::value;
+        if (fp8)
+            k_gramian<KT, true>
+                <<<grid_block(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                    indptr, indices, values, (const unsigned char*)factors,
+                    A_out, b_out, row_order, nrows, reg);
+        else
+            k_gramian<KT, false>
+                <<<grid_block(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                    indptr, indices, values, (const unsigned short*)factors,
+                    A_out, b_out, row_order, nrows, reg);
+        return hipGetLastError();
+    });
+}
+
+extern "C" int fma_cholesky_solve_ph(
+    int k, const float* A_in, const float* b_in, float* x_out,
+    long long nrows, int phases, void* stream) {
+    if (bad_shape(k, nrows)) return hipErrorInvalidValue;
+    return dispatch_ic<1, 2, 3, 4, 5, 6, 7, 8>(k / 16, [&](auto kt) {
+        k_cholesky_solve<decltype(kt)::value>
+            <<<grid_block(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                A_in, b_in, x_out, nrows, phases);
+        return hipGetLastError();
+    });
+}
+
+extern "C" int fma_cholesky_solve(
+    int k, const float* A_in, const float* b_in, float* x_out,
+    long long nrows, void* stream) {
+    return fma_cholesky_solve_ph(k, A_in, b_in, x_out, nrows, 3, stream);
+}
+
+extern "C" int fma_ldl_solve_wave(
+    int k, const float* A_in, const float* b_in, float* x_out,
+    unsigned short* x_bf16, unsigned char* x_fp8, long long nrows,
+    void* stream) {
+    if (bad_shape(k, nrows)) return hipErrorInvalidValue;
+    return dispatch_ic<1, 2, 3, 4>(k / 16, [&](auto kt) {
+        k_ldl_solve_wave<decltype(kt)::value>
+            <<<grid_wave(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                A_in, b_in, x_out, x_bf16, x_fp8, nrows);
+        return hipGetLastError();
+    });
+}
+
+// the intermediate ladder levels (PANEL, SUBST) exist for
+// k_als_solve_wavefused only
+extern "C" int fma_ldl_solve_wave_reg(
+    int k, const float* A_in, const float* b_in, float* x_out,
+    unsigned short* x_bf16, unsigned char* x_fp8, long long nrows,
+    int variant, void* stream) {
+    if (bad_shape(k, nrows)) return hipErrorInvalidValue;
+    return dispatch_ic<1, 2, 3, 4>(k / 16, [&](auto kt) {
+        constexpr int KT = decltype(kt)::value;
+        return dispatch_ic<WREG_BC_SHFL, WREG_BC_HOIST>(variant, [&](auto bc) {
+            k_ldl_solve_wave_reg<KT, decltype(bc)::value>
+                <<<grid_wave(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                    A_in, b_in, x_out, x_bf16, x_fp8, nrows);
+            return hipGetLastError();
+        });
+    });
+}
+
+extern "C" int fma_als_solve_wavefused_db(
+    int k, const long long* indptr, const int* indices, const float* values,
+    const void* factors, float* out_f32, unsigned short* out_bf16,
+    unsigned char* out_fp8, const int* row_order, long long nrows,
+    float reg, int variant, void* stream) {
+    if (bad_shape(k, nrows)) return hipErrorInvalidValue;
+    return dispatch_ic<1, 2, 3, 4>(k / 16, [&](auto kt) {
+        constexpr int KT = decltype(kt)::value;
+        return dispatch_ic<WREG_BC_SHFL, WREG_BC_HOIST>(variant, [&](auto bc) {
+            k_als_solve_wavefused_db<KT, decltype(bc)::value>
+                <<<grid_wave(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                    indptr, indices, values, factors, out_f32, out_bf16,
+                    out_fp8, row_order, nrows, reg);
+            return hipGetLastError();
+        });
+    });
+}
+
+extern "C" int fma_als_solve_wavefused(
+    int k, int fp8, const long long* indptr, const int* indices,
+    const float* values, const void* factors, float* out_f32,
+    unsigned short* out_bf16, unsigned char* out_fp8, const int* row_order,
+    long long nrows, float reg, int variant, void* stream) {
+    if (bad_shape(k, nrows)) return hipErrorInvalidValue;
+    return dispatch_ic<1, 2, 3, 4>(k / 16, [&](auto kt) {
+        constexpr int KT = decltype(kt)::value;
+        return dispatch_ic<WREG_BC_SHFL, WREG_BC_PANEL, WREG_BC_SUBST,
+                           WREG_BC_HOIST>(variant, [&](auto bc) {
+            constexpr int BC = decltype(bc)::value;
+            if (fp8)
+                k_als_solve_wavefused<KT, true, BC>
+                    <<<grid_wave(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                        indptr, indices, values, factors, out_f32, out_bf16,
+                        out_fp8, row_order, nrows, reg);
+            else
+                k_als_solve_wavefused<KT, false, BC>
+                    <<<grid_wave(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                        indptr, indices, values, factors, out_f32, out_bf16,
+                        out_fp8, row_order, nrows, reg);
+            return hipGetLastError();
+        });
+    });
+}
+
+extern "C" int fma_als_solve_wavefused2(
     int k, const long long* indptr, const int* indices, const float* values,
     const unsigned char* factors, float* out_f32, unsigned char* out_fp8,
-    const int* row_order, long long nrows, float reg, hipStream_t stream) {
-    if (k % 16 || k <= 64 || k > 128 || nrows <= 0)
-        return hipErrorInvalidValue;
-    dim3 grid((unsigned)nrows), block(256);
-    switch (k / 16) {
-        case 5: k_als_solve_wavefused2<5><<<grid, block, 0, stream>>>(indptr, indices, values, factors, out_f32, out_fp8, row_order, nrows, reg); break;
-        case 6: k_als_solve_wavefused2<6><<<grid, block, 0, stream>>>(indptr, indices, values, factors, out_f32, out_fp8, row_order, nrows, reg); break;
-        case 7: k_als_solve_wavefused2<7><<<grid, block, 0, stream>>>(indptr, indices, values, factors, out_f32, out_fp8, row_order, nrows, reg); break;
-        case 8: k_als_solve_wavefused2<8><<<grid, block, 0, stream>>>(indptr, indices, values, factors, out_f32, out_fp8, row_order, nrows, reg); break;
-        default: return hipErrorInvalidValue;
-    }
+    const int* row_order, long long nrows, float reg, void* stream) {
+    if (bad_shape(k, nrows)) return hipErrorInvalidValue;
+    return dispatch_ic<5, 6, 7, 8>(k / 16, [&](auto kt) {
+        k_als_solve_wavefused2<decltype(kt)::value>
+            <<<grid_block(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                indptr, indices, values, factors, out_f32, out_fp8,
+                row_order, nrows, reg);
+        return hipGetLastError();
+    });
+}
+
+extern "C" int fma_mfma_probe_f32(const float* A, const float* B, float* D,
+                                  void* stream) {
+    k_mfma_probe_f32<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>(A, B, D);
+    return hipGetLastError();
+}
+
+extern "C" int fma_mfma_probe_bf16(const unsigned short* Xt,
+                                   const unsigned short* Yt, float* C,
+                                   void* stream) {
+    k_mfma_probe_bf16<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>(Xt, Yt,
+                                                                     C);
+    return hipGetLastError();
+}
+
+extern "C" int fma_mfma_probe_fp8(const unsigned char* Xt,
+                                  const unsigned char* Yt, float* C,
+                                  void* stream) {
+    k_mfma_probe_fp8<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>(Xt, Yt,
+                                                                    C);
     return hipGetLastError();
 }

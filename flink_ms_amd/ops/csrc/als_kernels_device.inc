@@ -3,6 +3,8 @@
 // design commentary.
 #pragma once
 
+#include <type_traits>
+
 // ---------------------------------------------------------------- geometry
 
 template <int KT> struct Geo {
@@ -59,6 +61,12 @@ template <int KT> struct Geo {
 // fragment element type per gather precision
 template <bool FP8> struct FragT { using type = bf16x8; };
 template <> struct FragT<true> { using type = fp8x8; };
+
+// storage element of a factor image per gather precision (the gathered
+// factors and the low-precision copy of the solution): bf16 words or e4m3
+// bytes
+template <bool FP8> struct GatherT { using elem = unsigned short; };
+template <> struct GatherT<true> { using elem = unsigned char; };
 
 // triangular tile offset: tile (I,J), I >= J
 DEV_INLINE constexpr int tri_off(int I, int J) {
@@ -301,202 +309,22 @@ DEV_INLINE void write_acc_tri(const f32x4* acc, float* A, float* bhi,
     }
 }
 
-// ------------------------------------------------------ in-LDS Cholesky/solve
+// ------------------------------------------------------ in-LDS LDL^T/solve
 
-// In-place LDL^T elimination of the [K][K+1] LDS image (lower triangle),
-// 16-column panels, 256-thread block version (k up to 128; the k<=64 wave
-// solver in als_kernels.hip is the same algorithm without barriers):
-//   (a) panel factorization: thread r owns row r's 16-column segment in
-//       registers; the pivot column is broadcast through a small LDS
-//       scratch (one barrier per pivot);
+// In-place LDL^T elimination of the triangular LDS image (lower 16x16
+// tiles at tri_off, row stride Geo::LDT), 16-column panels, 256-thread
+// block version (k up to 128; the k<=64 wave solvers in als_kernels.hip are
+// the same algorithm without barriers):
+//   (a) panel factorization: wave 0 factors the whole panel slab in
+//       registers -- lane owns rows lane and lane+64, pivot column values
+//       broadcast by __shfl, no barriers inside the panel.  Rows above the
+//       panel have no storage in the triangular image and sit it out;
 //   (b) trailing update as f32 MFMA 16x16 tiles (v_mfma_f32_16x16x4_f32,
-//       exact fp32), tiles round-robined over the 4 waves.
-// Cells (r,c) with c > r are never-read upper-triangle scratch.
-// ``colbuf`` is a [16][16] float LDS scratch.
+//       exact fp32), tiles round-robined over the 4 waves, all 64 lanes
+//       live.  Diagonal tiles are kept in full: their upper halves are
+//       never-read scratch.
 template <int K>
-DEV_INLINE void cholesky_lds(float* A, float* colbuf) {
-    constexpr int NP = K / 16;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int li = lane & 15, g4 = lane >> 4;
-#pragma unroll 1
-    for (int pi = 0; pi < NP; ++pi) {
-        const int P0 = 16 * pi;
-        // ---- (a) wave 0 factors the whole panel slab in registers: lane
-        // owns rows lane and lane+64; pivot column values broadcast by
-        // __shfl -- no barriers inside the panel.
-        if (w == 0) {
-            float sa[16], sb[16];
-            const bool av = lane < K, bv = (K > 64) && (lane + 64 < K);
-            if (av) {
-#pragma unroll
-                for (int cc = 0; cc < 16; ++cc)
-                    sa[cc] = A[lane * (K + 1) + P0 + cc];
-            }
-            if (bv) {
-#pragma unroll
-                for (int cc = 0; cc < 16; ++cc)
-                    sb[cc] = A[(lane + 64) * (K + 1) + P0 + cc];
-            }
-#pragma unroll
-            for (int jj = 0; jj < 15; ++jj) {
-                const int j = P0 + jj;
-                const bool jhi = j >= 64;
-                const float dj = __shfl(jhi ? sb[jj] : sa[jj], j & 63, WAVE);
-                const float dinv = dj > 0.0f ? 1.0f / dj : 0.0f;
-                const float la = sa[jj] * dinv, lb = sb[jj] * dinv;
-#pragma unroll
-                for (int cc = jj + 1; cc < 16; ++cc) {
-                    const bool chi = P0 + cc >= 64;
-                    const float colj = __shfl(chi ? sb[jj] : sa[jj],
-                                              (P0 + cc) & 63, WAVE);
-                    sa[cc] -= la * colj;
-                    sb[cc] -= lb * colj;
-                }
-            }
-            if (av) {
-#pragma unroll
-                for (int cc = 0; cc < 16; ++cc)
-                    A[lane * (K + 1) + P0 + cc] = sa[cc];
-            }
-            if (bv) {
-#pragma unroll
-                for (int cc = 0; cc < 16; ++cc)
-                    A[(lane + 64) * (K + 1) + P0 + cc] = sb[cc];
-            }
-        }
-        __syncthreads();
-        if (pi == NP - 1) break;
-        // ---- (b) MFMA trailing update (all waves, all 64 lanes live)
-        float ndk[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int c = P0 + 4 * kk + g4;
-            const float d = A[c * (K + 1) + c];
-            ndk[kk] = d > 0.0f ? -1.0f / d : 0.0f;
-        }
-        int idx = 0;
-#pragma unroll 1
-        for (int rb = pi + 1; rb < NP; ++rb) {
-#pragma unroll 1
-            for (int cb = pi + 1; cb <= rb; ++cb) {
-                if ((idx++ & 3) != w) continue;
-                f32x4 acc;
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    acc[r] = A[(rb * 16 + g4 * 4 + r) * (K + 1) + cb * 16 + li];
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    const int pc = P0 + 4 * kk + g4;
-                    const float a = A[(rb * 16 + li) * (K + 1) + pc];
-                    const float b = A[(cb * 16 + li) * (K + 1) + pc] * ndk[kk];
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc,
-                                                               0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    A[(rb * 16 + g4 * 4 + r) * (K + 1) + cb * 16 + li] = acc[r];
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// Blocked triangular solves over the LDL^T image, 256 threads: thread r
-// owns row r's running value in a register; per 16-row block, the lanes of
-// wave 0 run the sequential in-block substitution (shfl chain) and publish
-// z through ``xbuf`` (LDS, >= K floats), then every thread applies the
-// block's contribution to its row with 16 fma.  Writes x (and optionally
-// bf16) straight to global.
-template <int K>
-DEV_INLINE void solve_lds_block(const float* A, const float* b, float* xbuf,
-                                float* x_row, unsigned short* xb_row) {
-    constexpr int NP = K / 16;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const bool own = tid < K;
-    float acc = own ? b[tid] : 0.0f;
-    const float dr = own ? A[tid * (K + 1) + tid] : 1.0f;
-    const float invd = dr > 0.0f ? 1.0f / dr : 0.0f;
-    // forward: (I + Ls) y = b, Ls[r][j] = A[r][j] / D_j
-#pragma unroll 1
-    for (int bi = 0; bi < NP; ++bi) {
-        const int B0 = 16 * bi;
-        if (own && tid >= B0 && tid < B0 + 16) xbuf[tid] = acc;
-        __syncthreads();
-        if (w == 0) {  // in-block substitution on lanes 0..15
-            const int r = B0 + (lane & 15);
-            float v = (lane < 16 && r < K) ? xbuf[r] : 0.0f;
-            float di = (lane < 16 && r < K) ? A[r * (K + 1) + r] : 1.0f;
-            di = di > 0.0f ? 1.0f / di : 0.0f;
-#pragma unroll
-            for (int t = 0; t < 15; ++t) {
-                const float zt = __shfl(v, t, WAVE) * __shfl(di, t, WAVE);
-                if (lane < 16 && lane > t && r < K)
-                    v -= A[r * (K + 1) + B0 + t] * zt;
-            }
-            if (lane < 16 && r < K) xbuf[r] = v * di;  // z_j = y_j / D_j
-        }
-        __syncthreads();
-        if (own && tid >= B0 + 16) {
-            float s = 0.0f;
-#pragma unroll
-            for (int cc = 0; cc < 16; ++cc)
-                s += A[tid * (K + 1) + B0 + cc] * xbuf[B0 + cc];
-            acc -= s;
-        } else if (own && tid >= B0 && tid < B0 + 16) {
-            acc = xbuf[tid] * dr;  // recover y_j from z_j
-        }
-        __syncthreads();
-    }
-    // w = y / D
-    acc *= invd;
-    // backward: (I + Ls^T) x = w ; Ls^T[j][c] = A[c][j] / D_j
-#pragma unroll 1
-    for (int bi = NP - 1; bi >= 0; --bi) {
-        const int B0 = 16 * bi;
-        if (own && tid >= B0 && tid < B0 + 16) xbuf[tid] = acc;
-        __syncthreads();
-        if (w == 0) {
-            const int r = B0 + (lane & 15);
-            float v = (lane < 16 && r < K) ? xbuf[r] : 0.0f;
-            float di = (lane < 16 && r < K) ? A[r * (K + 1) + r] : 1.0f;
-            di = di > 0.0f ? 1.0f / di : 0.0f;
-#pragma unroll
-            for (int t = 15; t >= 1; --t) {
-                const float xt = __shfl(v, t, WAVE);
-                if (lane < 16 && lane < t && r < K)
-                    v -= A[(B0 + t) * (K + 1) + r] * di * xt;
-            }
-            if (lane < 16 && r < K) xbuf[r] = v;
-        }
-        __syncthreads();
-        if (own && tid < B0) {
-            float s = 0.0f;
-#pragma unroll
-            for (int cc = 0; cc < 16; ++cc)
-                s += A[(B0 + cc) * (K + 1) + tid] * xbuf[B0 + cc];
-            acc -= s * invd;
-        } else if (own && tid >= B0 && tid < B0 + 16) {
-            acc = xbuf[tid];
-        }
-        __syncthreads();
-    }
-    if (own) {
-        x_row[tid] = acc;
-        if (xb_row) xb_row[tid] = f2bf(acc);
-    }
-}
-
-// Triangular-image variants of cholesky_lds / solve_lds_block: same
-// algorithm and barrier structure, A addressed as lower 16x16 tiles
-// (tri_off, stride Geo::LDT).  Rows above the current panel have no
-// storage and sit the factorization phase out (they are already-factored
-// rows; the square version let them compute upper-triangle scratch).
-template <int K>
-DEV_INLINE void cholesky_lds_tri(float* A, float* colbuf) {
+DEV_INLINE void cholesky_lds_tri(float* A) {
     constexpr int NP = K / 16;
     constexpr int LDT = Geo<K / 16>::LDT;
     constexpr int TSZ = Geo<K / 16>::TSZ;
@@ -504,7 +332,6 @@ DEV_INLINE void cholesky_lds_tri(float* A, float* colbuf) {
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int li = lane & 15, g4 = lane >> 4;
-    (void)colbuf;
 #pragma unroll 1
     for (int pi = 0; pi < NP; ++pi) {
         const int P0 = 16 * pi;
@@ -588,6 +415,12 @@ DEV_INLINE void cholesky_lds_tri(float* A, float* colbuf) {
     }
 }
 
+// Blocked triangular solves over the LDL^T image, 256 threads: thread r
+// owns row r's running value in a register; per 16-row block, the lanes of
+// wave 0 run the sequential in-block substitution (shfl chain) and publish
+// z through ``xbuf`` (LDS, >= K floats), then every thread applies the
+// block's contribution to its row with 16 fma.  Writes x, and its bf16 /
+// e4m3 image where ``xb_row`` / ``x8_row`` is non-null, straight to global.
 template <int K>
 DEV_INLINE void solve_lds_block_tri(const float* A, const float* b,
                                     float* xbuf, float* x_row,
@@ -774,27 +607,25 @@ DEV_INLINE int gramian_to_lds(char* smem,
     return n;
 }
 
-template <int KT>
-DEV_INLINE void write_zero_row(float* out_f32, unsigned short* out_bf16,
-                               long long row) {
+template <int KT, typename LP>
+DEV_INLINE void write_zero_row(float* out_f32, LP* out_lowp, long long row) {
     constexpr int K = Geo<KT>::K;
     for (int c = threadIdx.x; c < K; c += 256) {
         out_f32[row * K + c] = 0.0f;
-        if (out_bf16) out_bf16[row * K + c] = 0;
+        if (out_lowp) out_lowp[row * K + c] = 0;
     }
 }
 
-#define DISPATCH_KT(k, expr)                                                  \
-    switch ((k) / 16) {                                                       \
-        case 1: { constexpr int KT = 1; expr; break; }                        \
-        case 2: { constexpr int KT = 2; expr; break; }                        \
-        case 3: { constexpr int KT = 3; expr; break; }                        \
-        case 4: { constexpr int KT = 4; expr; break; }                        \
-        case 5: { constexpr int KT = 5; expr; break; }                        \
-        case 6: { constexpr int KT = 6; expr; break; }                        \
-        case 7: { constexpr int KT = 7; expr; break; }                        \
-        case 8: { constexpr int KT = 8; expr; break; }                        \
-        default: return hipErrorInvalidValue;                                 \
-    }
-
-
+// ------------------------------------------------------- launcher dispatch
+// Host side: maps a runtime value onto the compile-time list VS.  ``f`` is a
+// generic lambda called with std::integral_constant<int, V> for the V that
+// equals ``v`` and returns the launch status; a value outside the list is
+// hipErrorInvalidValue.  Nest two calls to pick (k/16, variant) pairs --
+// only the listed combinations are instantiated.
+template <int... VS, typename F>
+inline hipError_t dispatch_ic(int v, F&& f) {
+    hipError_t err = hipErrorInvalidValue;
+    (void)((v == VS &&
+            ((err = f(std::integral_constant<int, VS>{})), true)) || ...);
+    return err;
+}

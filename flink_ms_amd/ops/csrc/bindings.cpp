@@ -1,10 +1,14 @@
 // Python bindings for the flink_ms_amd HIP kernels.
 //
 // This translation unit is deliberately HIP-header-free: kernels live in the
-// .hip files behind extern "C" launchers (enum hipError_t <-> int,
-// hipStream_t <-> void*), so only hipcc ever sees device code and this file
+// .hip files behind the C launchers of fma_api.h (the one declaration both
+// sides compile against), so only hipcc ever sees device code and this file
 // only sees torch tensors.  The current HIP stream is passed in from Python
 // (torch.cuda.current_stream().cuda_stream).
+//
+// Every binding validates ALL of its tensors through one Args object before
+// it launches: the launchers take raw pointers, so a wrong device, dtype or
+// shape here would be an out-of-bounds access on the GPU, not an exception.
 
 #include <torch/extension.h>
 
@@ -14,87 +18,7 @@
 #include <thread>
 #include <vector>
 
-extern "C" {
-int fma_als_solve_fused(int k, const int64_t* indptr, const int* indices,
-                        const float* values, const unsigned short* factors,
-                        float* out_f32, unsigned short* out_bf16,
-                        const int* row_order, int64_t nrows, float reg,
-                        void* stream);
-int fma_gramian(int k, const int64_t* indptr, const int* indices,
-                const float* values, const unsigned short* factors,
-                float* A_out, float* b_out, const int* row_order,
-                int64_t nrows, float reg, void* stream);
-int fma_gramian_fp8(int k, const int64_t* indptr, const int* indices,
-                    const float* values, const unsigned char* factors,
-                    float* A_out, float* b_out, const int* row_order,
-                    int64_t nrows, float reg, void* stream);
-int fma_als_solve_fused_fp8(int k, const int64_t* indptr, const int* indices,
-                            const float* values, const unsigned char* factors,
-                            float* out_f32, unsigned char* out_fp8,
-                            const int* row_order, int64_t nrows, float reg,
-                            void* stream);
-int fma_cholesky_solve(int k, const float* A_in, const float* b_in,
-                       float* x_out, int64_t nrows, void* stream);
-int fma_cholesky_solve_ph(int k, const float* A_in, const float* b_in,
-                          float* x_out, int64_t nrows, int phases,
-                          void* stream);
-int fma_sdca_pass(const int64_t* indptr, const int* indices,
-                  const float* values, const float* y, const float* norms_sq,
-                  const int* perm, float* alpha, float* v, int64_t nrows,
-                  float scale, void* stream);
-long long fma_sdca_num_waves(long long nrows);
-int fma_svm_margins(const int64_t* indptr, const int* indices,
-                    const float* values, const float* w, float* out,
-                    int64_t nrows, void* stream);
-int fma_predict_dot(const unsigned short* U, const unsigned short* V,
-                    const int64_t* u_idx, const int64_t* i_idx,
-                    float* out, int64_t nq, int k, void* stream);
-int fma_sgd_update(unsigned short* U, unsigned short* V,
-                   const int64_t* u_idx, const int64_t* i_idx,
-                   const float* r, float* err_out, int64_t nq, int k,
-                   float lr, float user_reg, float item_reg, void* stream);
-int fma_als_solve_wavefused_db(int k, const int64_t* indptr,
-                               const int* indices, const float* values,
-                               const void* factors, float* out_f32,
-                               unsigned short* out_bf16,
-                               unsigned char* out_fp8,
-                               const int* row_order, int64_t nrows,
-                               float reg, int variant, void* stream);
-int fma_als_solve_wavefused(int k, int fp8, const int64_t* indptr,
-                            const int* indices, const float* values,
-                            const void* factors, float* out_f32,
-                            unsigned short* out_bf16, unsigned char* out_fp8,
-                            const int* row_order, int64_t nrows, float reg,
-                            int variant, void* stream);
-int fma_als_solve_wavefused2(int k, const int64_t* indptr,
-                             const int* indices, const float* values,
-                             const unsigned char* factors, float* out_f32,
-                             unsigned char* out_fp8, const int* row_order,
-                             int64_t nrows, float reg, void* stream);
-int fma_ldl_solve_wave(int k, const float* A_in, const float* b_in,
-                       float* x_out, unsigned short* x_bf16,
-                       unsigned char* x_fp8, int64_t nrows, void* stream);
-int fma_ldl_solve_wave_reg(int k, const float* A_in, const float* b_in,
-                           float* x_out, unsigned short* x_bf16,
-                           unsigned char* x_fp8, int64_t nrows,
-                           int variant, void* stream);
-int fma_mfma_probe_f32(const float* A, const float* B, float* D, void* stream);
-int fma_mfma_probe_bf16(const unsigned short* Xt, const unsigned short* Yt,
-                        float* C, void* stream);
-int fma_mfma_probe_fp8(const unsigned char* Xt, const unsigned char* Yt,
-                       float* C, void* stream);
-int fma_dbg_stage_dump(int k, const int64_t* indptr, const int* indices,
-                       const float* values, const unsigned short* factors,
-                       unsigned short* out, void* stream);
-int fma_dbg_frag_dump(int k, const int64_t* indptr, const int* indices,
-                      const float* values, const unsigned short* factors,
-                      unsigned short* out, void* stream);
-int fma_dbg_gramian(int k, const int64_t* indptr, const int* indices,
-                    const float* values, const unsigned short* factors,
-                    float* A_out, float* bhi_out, float* blo_out,
-                    int64_t nrows, float reg, void* stream);
-const char* fma_err_str(int err);
-}
+#include "fma_api.h"
 
 namespace {
 
@@ -213,353 +137,353 @@ void check_hip(int err, const char* what) {
     TORCH_CHECK(err == 0, what, " failed: ", fma_err_str(err));
 }
 
-void check_t(const torch::Tensor& t, torch::ScalarType dt, const char* name) {
-    TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-    TORCH_CHECK(t.scalar_type() == dt, name, " has wrong dtype");
+constexpr auto kF32 = torch::kFloat32;
+constexpr auto kBF16 = torch::kBFloat16;
+constexpr auto kU8 = torch::kUInt8;   // e4m3 factor images travel as bytes
+constexpr auto kI32 = torch::kInt32;
+constexpr auto kI64 = torch::kInt64;
+
+// Raw pointers for the launchers; the dtype was checked by Args.
+float* f32(const torch::Tensor& t) { return (float*)t.data_ptr(); }
+const int* i32(const torch::Tensor& t) { return (const int*)t.data_ptr(); }
+const long long* i64(const torch::Tensor& t) {
+    return (const long long*)t.data_ptr();
+}
+unsigned short* bf16(const torch::Tensor& t) {
+    return (unsigned short*)t.data_ptr();
+}
+unsigned char* u8(const torch::Tensor& t) {
+    return (unsigned char*)t.data_ptr();
 }
 
-const unsigned short* bf16_ptr(const torch::Tensor& t) {
-    TORCH_CHECK(t.scalar_type() == torch::kBFloat16,
-                "expected a bf16 tensor at the kernel boundary");
-    return reinterpret_cast<const unsigned short*>(t.data_ptr());
-}
-unsigned short* bf16_ptr_mut(torch::Tensor& t) {
-    TORCH_CHECK(t.scalar_type() == torch::kBFloat16,
-                "expected a bf16 output tensor at the kernel boundary");
-    return reinterpret_cast<unsigned short*>(t.data_ptr());
-}
+// The argument checks of one binding call.  Each tensor goes through
+// tensor() or optional() (dtype, contiguity) and the shape helpers: all of
+// that reads tensor metadata only.  stream() -- the one way a binding gets
+// the stream it must hand to its launcher -- then refuses unless every
+// tensor seen is on the GPU.  Every message starts with the binding's name
+// and names the argument.
+class Args {
+public:
+    explicit Args(const char* fn) : fn_(fn) {}
 
-// e4m3 factor images travel as uint8 byte tensors
-const unsigned char* fp8_ptr(const torch::Tensor& t) {
-    TORCH_CHECK(t.scalar_type() == torch::kUInt8,
-                "expected a uint8 (e4m3) tensor at the kernel boundary");
-    return reinterpret_cast<const unsigned char*>(t.data_ptr());
-}
-unsigned char* fp8_ptr_mut(torch::Tensor& t) {
-    TORCH_CHECK(t.scalar_type() == torch::kUInt8,
-                "expected a uint8 (e4m3) output tensor at the kernel boundary");
-    return reinterpret_cast<unsigned char*>(t.data_ptr());
-}
-
-const int* order_ptr(const torch::Tensor& row_order, int64_t nrows) {
-    if (row_order.numel() == 0) return nullptr;
-    TORCH_CHECK(row_order.scalar_type() == torch::kInt32 &&
-                row_order.is_cuda() && row_order.is_contiguous(),
-                "row_order must be contiguous int32 on GPU");
-    TORCH_CHECK(row_order.numel() == nrows, "row_order size");
-    return row_order.data_ptr<int>();
-}
-
-void als_solve_fused(torch::Tensor indptr, torch::Tensor indices,
-                     torch::Tensor values, torch::Tensor factors,
-                     torch::Tensor out_f32, torch::Tensor out_bf16,
-                     torch::Tensor row_order, double reg, int64_t stream) {
-    check_t(indptr, torch::kInt64, "indptr");
-    check_t(indices, torch::kInt32, "indices");
-    check_t(values, torch::kFloat32, "values");
-    check_t(factors, torch::kBFloat16, "factors");
-    check_t(out_f32, torch::kFloat32, "out_f32");
-    const int k = (int)factors.size(1);
-    const long long nrows = indptr.size(0) - 1;
-    TORCH_CHECK(out_f32.size(0) >= nrows && out_f32.size(1) == k,
-                "out_f32 shape mismatch");
-    unsigned short* ob = nullptr;
-    if (out_bf16.numel() > 0) {
-        check_t(out_bf16, torch::kBFloat16, "out_bf16");
-        TORCH_CHECK(out_bf16.numel() >= out_f32.numel(), "out_bf16 shape");
-        ob = bf16_ptr_mut(out_bf16);
+    void tensor(const torch::Tensor& t, torch::ScalarType dt,
+                const char* name) {
+        TORCH_CHECK(t.scalar_type() == dt, fn_, ": ", name, " must be ", dt,
+                    ", got ", t.scalar_type());
+        TORCH_CHECK(t.is_contiguous(), fn_, ": ", name,
+                    " must be contiguous");
+        if (!t.is_cuda() && !off_gpu_) off_gpu_ = name;
     }
-    const int* order = nullptr;
-    if (row_order.numel() > 0) {
-        check_t(row_order, torch::kInt32, "row_order");
-        TORCH_CHECK(row_order.numel() == nrows, "row_order size");
-        order = row_order.data_ptr<int>();
+
+    // optional tensor: empty means absent (any dtype or device); present
+    // means dt, contiguous, at least min_numel elements
+    bool optional(const torch::Tensor& t, torch::ScalarType dt,
+                  const char* name, int64_t min_numel) {
+        if (t.numel() == 0) return false;
+        tensor(t, dt, name);
+        TORCH_CHECK(t.numel() >= min_numel, fn_, ": ", name,
+                    " must be empty or have at least ", min_numel,
+                    " elements, got ", t.numel());
+        return true;
     }
-    check_hip(fma_als_solve_fused(
-                  k, indptr.data_ptr<int64_t>(), indices.data_ptr<int>(),
-                  values.data_ptr<float>(), bf16_ptr(factors),
-                  out_f32.data_ptr<float>(), ob, order, nrows, (float)reg,
-                  (void*)stream),
-              "als_solve_fused");
-}
 
-void gramian(torch::Tensor indptr, torch::Tensor indices, torch::Tensor values,
-             torch::Tensor factors, torch::Tensor A_out, torch::Tensor b_out,
-             torch::Tensor row_order, double reg, int64_t stream) {
-    check_t(indptr, torch::kInt64, "indptr");
-    check_t(indices, torch::kInt32, "indices");
-    check_t(values, torch::kFloat32, "values");
-    check_t(factors, torch::kBFloat16, "factors");
-    check_t(A_out, torch::kFloat32, "A_out");
-    check_t(b_out, torch::kFloat32, "b_out");
-    const int k = (int)factors.size(1);
-    const long long nrows = indptr.size(0) - 1;
-    check_hip(fma_gramian(k, indptr.data_ptr<int64_t>(),
-                          indices.data_ptr<int>(), values.data_ptr<float>(),
-                          bf16_ptr(factors), A_out.data_ptr<float>(),
-                          b_out.data_ptr<float>(),
-                          order_ptr(row_order, nrows), nrows, (float)reg,
-                          (void*)stream),
-              "gramian");
-}
-
-void gramian_fp8(torch::Tensor indptr, torch::Tensor indices,
-                 torch::Tensor values, torch::Tensor factors,
-                 torch::Tensor A_out, torch::Tensor b_out,
-                 torch::Tensor row_order, double reg, int64_t stream) {
-    check_t(indptr, torch::kInt64, "indptr");
-    check_t(indices, torch::kInt32, "indices");
-    check_t(values, torch::kFloat32, "values");
-    check_t(factors, torch::kUInt8, "factors");
-    check_t(A_out, torch::kFloat32, "A_out");
-    check_t(b_out, torch::kFloat32, "b_out");
-    const int k = (int)factors.size(1);
-    const long long nrows = indptr.size(0) - 1;
-    check_hip(fma_gramian_fp8(
-                  k, indptr.data_ptr<int64_t>(), indices.data_ptr<int>(),
-                  values.data_ptr<float>(), fp8_ptr(factors),
-                  A_out.data_ptr<float>(), b_out.data_ptr<float>(),
-                  order_ptr(row_order, nrows), nrows, (float)reg,
-                  (void*)stream),
-              "gramian_fp8");
-}
-
-void als_solve_fused_fp8(torch::Tensor indptr, torch::Tensor indices,
-                         torch::Tensor values, torch::Tensor factors,
-                         torch::Tensor out_f32, torch::Tensor out_fp8,
-                         torch::Tensor row_order, double reg,
-                         int64_t stream) {
-    check_t(indptr, torch::kInt64, "indptr");
-    check_t(indices, torch::kInt32, "indices");
-    check_t(values, torch::kFloat32, "values");
-    check_t(factors, torch::kUInt8, "factors");
-    check_t(out_f32, torch::kFloat32, "out_f32");
-    const int k = (int)factors.size(1);
-    const long long nrows = indptr.size(0) - 1;
-    TORCH_CHECK(out_f32.size(0) >= nrows && out_f32.size(1) == k,
-                "out_f32 shape mismatch");
-    unsigned char* o8 = nullptr;
-    if (out_fp8.numel() > 0) {
-        check_t(out_fp8, torch::kUInt8, "out_fp8");
-        TORCH_CHECK(out_fp8.numel() >= out_f32.numel(), "out_fp8 shape");
-        o8 = fp8_ptr_mut(out_fp8);
+    // CSR triple; returns nrows
+    int64_t csr(const torch::Tensor& indptr, const torch::Tensor& indices,
+                const torch::Tensor& values) {
+        tensor(indptr, kI64, "indptr");
+        tensor(indices, kI32, "indices");
+        tensor(values, kF32, "values");
+        TORCH_CHECK(indptr.dim() == 1 && indptr.numel() >= 1, fn_,
+                    ": indptr must be 1-D with nrows + 1 elements");
+        TORCH_CHECK(indices.dim() == 1 && values.dim() == 1 &&
+                        indices.numel() == values.numel(),
+                    fn_, ": indices and values must be 1-D of one length");
+        return indptr.numel() - 1;
     }
-    check_hip(fma_als_solve_fused_fp8(
-                  k, indptr.data_ptr<int64_t>(), indices.data_ptr<int>(),
-                  values.data_ptr<float>(), fp8_ptr(factors),
-                  out_f32.data_ptr<float>(), o8, order_ptr(row_order, nrows),
-                  nrows, (float)reg, (void*)stream),
-              "als_solve_fused_fp8");
-}
 
-void cholesky_solve_ph(torch::Tensor A, torch::Tensor b, torch::Tensor x,
-                       int64_t phases, int64_t stream) {
-    check_hip(fma_cholesky_solve_ph((int)A.size(1), A.data_ptr<float>(),
-                                    b.data_ptr<float>(), x.data_ptr<float>(),
-                                    A.size(0), (int)phases, (void*)stream),
-              "cholesky_solve_ph");
-}
+    // gathered factor matrix [n][k], bf16 or (uint8) e4m3; returns k
+    int factors(const torch::Tensor& t, bool fp8, const char* name) {
+        tensor(t, fp8 ? kU8 : kBF16, name);
+        TORCH_CHECK(t.dim() == 2, fn_, ": ", name, " must be 2-D");
+        return rank(t.size(1), name);
+    }
+
+    // batched systems A [n][k][k]; returns k
+    int systems(const torch::Tensor& A, const char* name) {
+        tensor(A, kF32, name);
+        TORCH_CHECK(A.dim() == 3 && A.size(1) == A.size(2), fn_, ": ", name,
+                    " must be [n][k][k]");
+        return rank(A.size(1), name);
+    }
+
+    // dt matrix with at least nrows rows and exactly k columns
+    void rows(const torch::Tensor& t, torch::ScalarType dt, const char* name,
+              int64_t nrows, int k) {
+        tensor(t, dt, name);
+        TORCH_CHECK(t.dim() == 2 && t.size(0) >= nrows && t.size(1) == k, fn_,
+                    ": ", name, " must be [>= ", nrows, "][", k, "], got ",
+                    t.sizes());
+    }
+
+    // fp32 [>= nrows][k][k] (the Gramian's A output)
+    void square_rows(const torch::Tensor& t, const char* name, int64_t nrows,
+                     int k) {
+        tensor(t, kF32, name);
+        TORCH_CHECK(t.dim() == 3 && t.size(0) >= nrows && t.size(1) == k &&
+                        t.size(2) == k,
+                    fn_, ": ", name, " must be [>= ", nrows, "][", k, "][", k,
+                    "], got ", t.sizes());
+    }
+
+    // flat buffer of exactly / at least n elements
+    void flat(const torch::Tensor& t, torch::ScalarType dt, const char* name,
+              int64_t n, bool exact) {
+        tensor(t, dt, name);
+        TORCH_CHECK(exact ? t.numel() == n : t.numel() >= n, fn_, ": ", name,
+                    " must have ", exact ? "" : "at least ", n,
+                    " elements, got ", t.numel());
+    }
+
+    // optional launch schedule: empty, or int32 of length nrows
+    const int* row_order(const torch::Tensor& t, int64_t nrows,
+                         const char* name = "row_order") {
+        if (t.numel() == 0) return nullptr;
+        tensor(t, kI32, name);
+        TORCH_CHECK(t.dim() == 1 && t.numel() == nrows, fn_, ": ", name,
+                    " must be empty or 1-D with nrows = ", nrows,
+                    " elements, got ", t.numel());
+        return i32(t);
+    }
+
+    void* stream(int64_t s) const {
+        TORCH_CHECK(!off_gpu_, fn_, ": ", off_gpu_ ? off_gpu_ : "",
+                    " must be on the GPU");
+        return (void*)s;
+    }
+
+    const char* name() const { return fn_; }
+
+private:
+    int rank(int64_t k, const char* name) {
+        TORCH_CHECK(k > 0 && k % 16 == 0, fn_, ": ", name, " has rank ", k,
+                    ", need a multiple of 16");
+        return (int)k;
+    }
+
+    const char* fn_;
+    const char* off_gpu_ = nullptr;   // first tensor seen off the GPU
+};
+
+// The low-precision images written beside an fp32 [rows][k] output: each
+// empty, or typed and at least as large as that output.
+struct LowpOut {
+    unsigned short* bf16p = nullptr;
+    unsigned char* fp8p = nullptr;
+    LowpOut(Args& a, const torch::Tensor& out_f32,
+            const torch::Tensor& out_bf16, const char* bf16_name,
+            const torch::Tensor& out_fp8, const char* fp8_name) {
+        if (a.optional(out_bf16, kBF16, bf16_name, out_f32.numel()))
+            bf16p = bf16(out_bf16);
+        if (a.optional(out_fp8, kU8, fp8_name, out_f32.numel()))
+            fp8p = u8(out_fp8);
+    }
+};
+
+// ------------------------------------------------------------------- ALS
 
 // Lane-broadcast variant of the register LDL (WREG_BC_* in
 // als_kernels.hip): 0 = the __shfl path kept as the measured baseline,
 // 3 = readlane broadcasts + branch-free substitutions (the default), 1 and
 // 2 = the intermediate ladder steps (k_als_solve_wavefused only).  Every
-// variant computes bit-identical results.  Each binding below also keeps
-// its variant-less signature, which runs the default.
+// variant computes bit-identical results; ``variant`` is the last, optional
+// argument of the bindings that take one.
 constexpr int64_t kBroadcastShfl = 0;
 constexpr int64_t kBroadcastDefault = 3;
 
-// single-kernel k<=64 path: Gramian + register LDL in one wave per entity
-// (no A materialization in HBM).  factors dtype selects bf16 vs e4m3.
-void als_solve_wavefused_v(torch::Tensor indptr, torch::Tensor indices,
-                           torch::Tensor values, torch::Tensor factors,
-                           torch::Tensor out_f32, torch::Tensor out_bf16,
-                           torch::Tensor out_fp8, torch::Tensor row_order,
-                           double reg, int64_t stream, int64_t variant) {
-    check_t(indptr, torch::kInt64, "indptr");
-    check_t(indices, torch::kInt32, "indices");
-    check_t(values, torch::kFloat32, "values");
-    check_t(out_f32, torch::kFloat32, "out_f32");
-    const bool fp8 = factors.scalar_type() == torch::kUInt8;
-    if (!fp8) check_t(factors, torch::kBFloat16, "factors");
-    TORCH_CHECK(factors.is_cuda() && factors.is_contiguous(),
-                "factors must be contiguous on GPU");
-    const int k = (int)factors.size(1);
-    const long long nrows = indptr.size(0) - 1;
-    TORCH_CHECK(out_f32.size(0) >= nrows && out_f32.size(1) == k,
-                "out_f32 shape mismatch");
-    unsigned short* ob = nullptr;
-    if (out_bf16.numel() > 0) {
-        TORCH_CHECK(out_bf16.numel() >= out_f32.numel(), "out_bf16 shape");
-        ob = bf16_ptr_mut(out_bf16);
-    }
-    unsigned char* o8 = nullptr;
-    if (out_fp8.numel() > 0) {
-        TORCH_CHECK(out_fp8.numel() >= out_f32.numel(), "out_fp8 shape");
-        o8 = fp8_ptr_mut(out_fp8);
-    }
-    check_hip(fma_als_solve_wavefused(
-                  k, fp8 ? 1 : 0, indptr.data_ptr<int64_t>(),
-                  indices.data_ptr<int>(), values.data_ptr<float>(),
-                  factors.data_ptr(), out_f32.data_ptr<float>(), ob, o8,
-                  order_ptr(row_order, nrows), nrows, (float)reg,
-                  (int)variant, (void*)stream),
-              "als_solve_wavefused");
+// block-fused path (k <= 128).  The factors' dtype selects bf16 vs e4m3
+// gathers and, with it, the one low-precision image the kernel writes.
+void als_solve_fused(torch::Tensor indptr, torch::Tensor indices,
+                     torch::Tensor values, torch::Tensor factors,
+                     torch::Tensor out_f32, torch::Tensor out_bf16,
+                     torch::Tensor out_fp8, torch::Tensor row_order,
+                     double reg, int64_t stream) {
+    Args a("als_solve_fused");
+    const int64_t nrows = a.csr(indptr, indices, values);
+    const bool fp8 = factors.scalar_type() == kU8;
+    const int k = a.factors(factors, fp8, "factors");
+    a.rows(out_f32, kF32, "out_f32", nrows, k);
+    const LowpOut lp(a, out_f32, out_bf16, "out_bf16", out_fp8, "out_fp8");
+    TORCH_CHECK(fp8 ? !lp.bf16p : !lp.fp8p, a.name(), ": ",
+                fp8 ? "out_bf16 must be empty with e4m3 factors"
+                    : "out_fp8 must be empty with bf16 factors");
+    const int* order = a.row_order(row_order, nrows);
+    check_hip(fma_als_solve_fused(k, fp8, i64(indptr), i32(indices),
+                                  f32(values), factors.data_ptr(),
+                                  f32(out_f32), lp.bf16p, lp.fp8p, order,
+                                  nrows, (float)reg, a.stream(stream)),
+              a.name());
 }
 
+void gramian(torch::Tensor indptr, torch::Tensor indices, torch::Tensor values,
+             torch::Tensor factors, torch::Tensor A_out, torch::Tensor b_out,
+             torch::Tensor row_order, double reg, int64_t stream) {
+    Args a("gramian");
+    const int64_t nrows = a.csr(indptr, indices, values);
+    const bool fp8 = factors.scalar_type() == kU8;
+    const int k = a.factors(factors, fp8, "factors");
+    a.square_rows(A_out, "A_out", nrows, k);
+    a.rows(b_out, kF32, "b_out", nrows, k);
+    const int* order = a.row_order(row_order, nrows);
+    check_hip(fma_gramian(k, fp8, i64(indptr), i32(indices), f32(values),
+                          factors.data_ptr(), f32(A_out), f32(b_out), order,
+                          nrows, (float)reg, a.stream(stream)),
+              a.name());
+}
+
+// single-kernel k<=64 path: Gramian + register LDL in one wave per entity
+// (no A materialization in HBM).  factors dtype selects bf16 vs e4m3.
 void als_solve_wavefused(torch::Tensor indptr, torch::Tensor indices,
                          torch::Tensor values, torch::Tensor factors,
                          torch::Tensor out_f32, torch::Tensor out_bf16,
                          torch::Tensor out_fp8, torch::Tensor row_order,
-                         double reg, int64_t stream) {
-    als_solve_wavefused_v(indptr, indices, values, factors, out_f32,
-                          out_bf16, out_fp8, row_order, reg, stream,
-                          kBroadcastDefault);
+                         double reg, int64_t stream, int64_t variant) {
+    Args a("als_solve_wavefused");
+    const int64_t nrows = a.csr(indptr, indices, values);
+    const bool fp8 = factors.scalar_type() == kU8;
+    const int k = a.factors(factors, fp8, "factors");
+    a.rows(out_f32, kF32, "out_f32", nrows, k);
+    const LowpOut lp(a, out_f32, out_bf16, "out_bf16", out_fp8, "out_fp8");
+    const int* order = a.row_order(row_order, nrows);
+    check_hip(fma_als_solve_wavefused(
+                  k, fp8, i64(indptr), i32(indices), f32(values),
+                  factors.data_ptr(), f32(out_f32), lp.bf16p, lp.fp8p, order,
+                  nrows, (float)reg, (int)variant, a.stream(stream)),
+              a.name());
 }
 
-// double-buffered variant (fp8 only): software-pipelined staging
-void als_solve_wavefused_db_v(torch::Tensor indptr, torch::Tensor indices,
-                              torch::Tensor values, torch::Tensor factors,
-                              torch::Tensor out_f32, torch::Tensor out_bf16,
-                              torch::Tensor out_fp8, torch::Tensor row_order,
-                              double reg, int64_t stream, int64_t variant) {
-    check_t(indptr, torch::kInt64, "indptr");
-    check_t(indices, torch::kInt32, "indices");
-    check_t(values, torch::kFloat32, "values");
-    check_t(factors, torch::kUInt8, "factors");
-    check_t(out_f32, torch::kFloat32, "out_f32");
-    const int k = (int)factors.size(1);
-    const long long nrows = indptr.size(0) - 1;
-    TORCH_CHECK(out_f32.size(0) >= nrows && out_f32.size(1) == k,
-                "out_f32 shape mismatch");
-    unsigned short* ob = nullptr;
-    if (out_bf16.numel() > 0) ob = bf16_ptr_mut(out_bf16);
-    unsigned char* o8 = nullptr;
-    if (out_fp8.numel() > 0) o8 = fp8_ptr_mut(out_fp8);
-    check_hip(fma_als_solve_wavefused_db(
-                  k, indptr.data_ptr<int64_t>(), indices.data_ptr<int>(),
-                  values.data_ptr<float>(), factors.data_ptr(),
-                  out_f32.data_ptr<float>(), ob, o8,
-                  order_ptr(row_order, nrows), nrows, (float)reg,
-                  (int)variant, (void*)stream),
-              "als_solve_wavefused_db");
-}
-
+// double-buffered variant (e4m3 only): software-pipelined staging
 void als_solve_wavefused_db(torch::Tensor indptr, torch::Tensor indices,
                             torch::Tensor values, torch::Tensor factors,
                             torch::Tensor out_f32, torch::Tensor out_bf16,
                             torch::Tensor out_fp8, torch::Tensor row_order,
-                            double reg, int64_t stream) {
-    als_solve_wavefused_db_v(indptr, indices, values, factors, out_f32,
-                             out_bf16, out_fp8, row_order, reg, stream,
-                             kBroadcastDefault);
+                            double reg, int64_t stream, int64_t variant) {
+    Args a("als_solve_wavefused_db");
+    const int64_t nrows = a.csr(indptr, indices, values);
+    const int k = a.factors(factors, /*fp8=*/true, "factors");
+    a.rows(out_f32, kF32, "out_f32", nrows, k);
+    const LowpOut lp(a, out_f32, out_bf16, "out_bf16", out_fp8, "out_fp8");
+    const int* order = a.row_order(row_order, nrows);
+    check_hip(fma_als_solve_wavefused_db(
+                  k, i64(indptr), i32(indices), f32(values),
+                  factors.data_ptr(), f32(out_f32), lp.bf16p, lp.fp8p, order,
+                  nrows, (float)reg, (int)variant, a.stream(stream)),
+              a.name());
 }
 
-// wave-pair fused path for 64 < k <= 128 (fp8 gathers only)
+// wave-quad fused path for 64 < k <= 128 (e4m3 gathers only)
 void als_solve_wavefused2(torch::Tensor indptr, torch::Tensor indices,
                           torch::Tensor values, torch::Tensor factors,
                           torch::Tensor out_f32, torch::Tensor out_fp8,
                           torch::Tensor row_order, double reg,
                           int64_t stream) {
-    check_t(indptr, torch::kInt64, "indptr");
-    check_t(indices, torch::kInt32, "indices");
-    check_t(values, torch::kFloat32, "values");
-    check_t(factors, torch::kUInt8, "factors");
-    check_t(out_f32, torch::kFloat32, "out_f32");
-    const int k = (int)factors.size(1);
-    const long long nrows = indptr.size(0) - 1;
-    TORCH_CHECK(out_f32.size(0) == nrows && out_f32.size(1) == k,
-                "out_f32 shape mismatch");
-    unsigned char* o8 = nullptr;
-    if (out_fp8.numel() > 0) {
-        TORCH_CHECK(out_fp8.numel() == out_f32.numel(), "out_fp8 shape");
-        o8 = fp8_ptr_mut(out_fp8);
-    }
+    Args a("als_solve_wavefused2");
+    const int64_t nrows = a.csr(indptr, indices, values);
+    const int k = a.factors(factors, /*fp8=*/true, "factors");
+    a.rows(out_f32, kF32, "out_f32", nrows, k);
+    unsigned char* o8 =
+        a.optional(out_fp8, kU8, "out_fp8", out_f32.numel()) ? u8(out_fp8)
+                                                             : nullptr;
+    const int* order = a.row_order(row_order, nrows);
     check_hip(fma_als_solve_wavefused2(
-                  k, indptr.data_ptr<int64_t>(), indices.data_ptr<int>(),
-                  values.data_ptr<float>(), fp8_ptr(factors),
-                  out_f32.data_ptr<float>(), o8, order_ptr(row_order, nrows),
-                  nrows, (float)reg, (void*)stream),
-              "als_solve_wavefused2");
+                  k, i64(indptr), i32(indices), f32(values), u8(factors),
+                  f32(out_f32), o8, order, nrows, (float)reg,
+                  a.stream(stream)),
+              a.name());
 }
 
-void ldl_solve_wave(torch::Tensor A, torch::Tensor b, torch::Tensor x,
-                    torch::Tensor x_bf16, torch::Tensor x_fp8,
-                    int64_t stream) {
-    unsigned short* xb = x_bf16.numel() > 0 ? bf16_ptr_mut(x_bf16) : nullptr;
-    unsigned char* x8 = x_fp8.numel() > 0 ? fp8_ptr_mut(x_fp8) : nullptr;
-    check_hip(fma_ldl_solve_wave((int)A.size(1), A.data_ptr<float>(),
-                                 b.data_ptr<float>(), x.data_ptr<float>(),
-                                 xb, x8, A.size(0), (void*)stream),
-              "ldl_solve_wave");
+// Batched solves A x = b from dense systems: A [n][k][k], b and x
+// [>= n][k].  Returns (n, k) through the out-parameters.
+void solve_args(Args& a, const torch::Tensor& A, const torch::Tensor& b,
+                const torch::Tensor& x, int64_t& nrows, int& k) {
+    k = a.systems(A, "A");
+    nrows = A.size(0);
+    a.rows(b, kF32, "b", nrows, k);
+    a.rows(x, kF32, "x", nrows, k);
 }
 
-// register-resident v2 (A in MFMA fragments, panel scratch in LDS)
-void ldl_solve_wave_reg_v(torch::Tensor A, torch::Tensor b, torch::Tensor x,
-                          torch::Tensor x_bf16, torch::Tensor x_fp8,
-                          int64_t stream, int64_t variant) {
-    unsigned short* xb = x_bf16.numel() > 0 ? bf16_ptr_mut(x_bf16) : nullptr;
-    unsigned char* x8 = x_fp8.numel() > 0 ? fp8_ptr_mut(x_fp8) : nullptr;
-    check_hip(fma_ldl_solve_wave_reg((int)A.size(1), A.data_ptr<float>(),
-                                     b.data_ptr<float>(), x.data_ptr<float>(),
-                                     xb, x8, A.size(0), (int)variant,
-                                     (void*)stream),
-              "ldl_solve_wave_reg");
-}
-
-void ldl_solve_wave_reg(torch::Tensor A, torch::Tensor b, torch::Tensor x,
-                        torch::Tensor x_bf16, torch::Tensor x_fp8,
-                        int64_t stream) {
-    ldl_solve_wave_reg_v(A, b, x, x_bf16, x_fp8, stream, kBroadcastDefault);
+// phases bitmask (debug/ablation): 1 = eliminate, 2 = substitute
+void cholesky_solve_ph(torch::Tensor A, torch::Tensor b, torch::Tensor x,
+                       int64_t phases, int64_t stream) {
+    Args a("cholesky_solve_ph");
+    int64_t nrows;
+    int k;
+    solve_args(a, A, b, x, nrows, k);
+    TORCH_CHECK(phases >= 0 && phases <= 3, a.name(),
+                ": phases must be in 0..3, got ", phases);
+    check_hip(fma_cholesky_solve_ph(k, f32(A), f32(b), f32(x), nrows,
+                                    (int)phases, a.stream(stream)),
+              a.name());
 }
 
 void cholesky_solve(torch::Tensor A, torch::Tensor b, torch::Tensor x,
                     int64_t stream) {
-    check_t(A, torch::kFloat32, "A");
-    check_t(b, torch::kFloat32, "b");
-    check_t(x, torch::kFloat32, "x");
-    const long long nrows = A.size(0);
-    const int k = (int)A.size(1);
-    check_hip(fma_cholesky_solve(k, A.data_ptr<float>(), b.data_ptr<float>(),
-                                 x.data_ptr<float>(), nrows, (void*)stream),
-              "cholesky_solve");
+    Args a("cholesky_solve");
+    int64_t nrows;
+    int k;
+    solve_args(a, A, b, x, nrows, k);
+    check_hip(fma_cholesky_solve(k, f32(A), f32(b), f32(x), nrows,
+                                 a.stream(stream)),
+              a.name());
 }
+
+// wave-per-entity LDL over an LDS image (v1, k <= 64)
+void ldl_solve_wave(torch::Tensor A, torch::Tensor b, torch::Tensor x,
+                    torch::Tensor x_bf16, torch::Tensor x_fp8,
+                    int64_t stream) {
+    Args a("ldl_solve_wave");
+    int64_t nrows;
+    int k;
+    solve_args(a, A, b, x, nrows, k);
+    const LowpOut lp(a, x, x_bf16, "x_bf16", x_fp8, "x_fp8");
+    check_hip(fma_ldl_solve_wave(k, f32(A), f32(b), f32(x), lp.bf16p, lp.fp8p,
+                                 nrows, a.stream(stream)),
+              a.name());
+}
+
+// register-resident v2 (A in MFMA fragments, panel scratch in LDS)
+void ldl_solve_wave_reg(torch::Tensor A, torch::Tensor b, torch::Tensor x,
+                        torch::Tensor x_bf16, torch::Tensor x_fp8,
+                        int64_t stream, int64_t variant) {
+    Args a("ldl_solve_wave_reg");
+    int64_t nrows;
+    int k;
+    solve_args(a, A, b, x, nrows, k);
+    const LowpOut lp(a, x, x_bf16, "x_bf16", x_fp8, "x_fp8");
+    check_hip(fma_ldl_solve_wave_reg(k, f32(A), f32(b), f32(x), lp.bf16p,
+                                     lp.fp8p, nrows, (int)variant,
+                                     a.stream(stream)),
+              a.name());
+}
+
+// ------------------------------------------------------------------- SVM
 
 void sdca_pass(torch::Tensor indptr, torch::Tensor indices,
                torch::Tensor values, torch::Tensor y, torch::Tensor norms_sq,
                torch::Tensor perm, torch::Tensor alpha, torch::Tensor v,
                double scale, int64_t stream) {
-    check_t(indptr, torch::kInt64, "indptr");
-    check_t(indices, torch::kInt32, "indices");
-    check_t(values, torch::kFloat32, "values");
-    check_t(y, torch::kFloat32, "y");
-    check_t(norms_sq, torch::kFloat32, "norms_sq");
-    check_t(alpha, torch::kFloat32, "alpha");
-    check_t(v, torch::kFloat32, "v");
-    const int* p = nullptr;
-    if (perm.numel() > 0) {
-        check_t(perm, torch::kInt32, "perm");
-        p = perm.data_ptr<int>();
-    }
+    Args a("sdca_pass");
     // the kernel indexes all per-sample arrays by row id: sizes must agree
     // before anything is launched
-    TORCH_CHECK(indptr.numel() >= 1, "indptr must have nrows + 1 elements");
-    const int64_t nrows = indptr.numel() - 1;
-    TORCH_CHECK(y.numel() == nrows, "y must have nrows elements");
-    TORCH_CHECK(norms_sq.numel() == nrows,
-                "norms_sq must have nrows elements");
-    TORCH_CHECK(alpha.numel() == nrows, "alpha must have nrows elements");
-    TORCH_CHECK(perm.numel() == 0 || perm.numel() == nrows,
-                "perm must be empty or have nrows elements");
-    TORCH_CHECK(indices.numel() == values.numel(),
-                "indices and values must have the same length");
-    check_hip(fma_sdca_pass(indptr.data_ptr<int64_t>(),
-                            indices.data_ptr<int>(), values.data_ptr<float>(),
-                            y.data_ptr<float>(), norms_sq.data_ptr<float>(),
-                            p, alpha.data_ptr<float>(), v.data_ptr<float>(),
-                            nrows, (float)scale, (void*)stream),
-              "sdca_pass");
+    const int64_t nrows = a.csr(indptr, indices, values);
+    a.flat(y, kF32, "y", nrows, /*exact=*/true);
+    a.flat(norms_sq, kF32, "norms_sq", nrows, true);
+    a.flat(alpha, kF32, "alpha", nrows, true);
+    a.tensor(v, kF32, "v");
+    const int* p = a.row_order(perm, nrows, "perm");
+    check_hip(fma_sdca_pass(i64(indptr), i32(indices), f32(values), f32(y),
+                            f32(norms_sq), p, f32(alpha), f32(v), nrows,
+                            (float)scale, a.stream(stream)),
+              a.name());
 }
 
 // Waves one sdca_pass launch over nrows samples runs with (the stride of the
@@ -571,135 +495,134 @@ int64_t sdca_num_waves(int64_t nrows) {
 void svm_margins(torch::Tensor indptr, torch::Tensor indices,
                  torch::Tensor values, torch::Tensor w, torch::Tensor out,
                  int64_t stream) {
-    check_t(indptr, torch::kInt64, "indptr");
-    check_t(indices, torch::kInt32, "indices");
-    check_t(values, torch::kFloat32, "values");
-    check_t(w, torch::kFloat32, "w");
-    check_t(out, torch::kFloat32, "out");
-    TORCH_CHECK(indptr.numel() >= 1, "indptr must have nrows + 1 elements");
-    TORCH_CHECK(out.numel() >= indptr.numel() - 1,
-                "out must have at least nrows elements");
-    check_hip(fma_svm_margins(indptr.data_ptr<int64_t>(),
-                              indices.data_ptr<int>(),
-                              values.data_ptr<float>(), w.data_ptr<float>(),
-                              out.data_ptr<float>(), indptr.size(0) - 1,
-                              (void*)stream),
-              "svm_margins");
+    Args a("svm_margins");
+    const int64_t nrows = a.csr(indptr, indices, values);
+    a.tensor(w, kF32, "w");
+    a.flat(out, kF32, "out", nrows, /*exact=*/false);
+    check_hip(fma_svm_margins(i64(indptr), i32(indices), f32(values), f32(w),
+                              f32(out), nrows, a.stream(stream)),
+              a.name());
+}
+
+// --------------------------------------------------------------- serving
+
+// U, V bf16 [n][k] of one rank; u_idx, i_idx int64 of one length.  Returns
+// the number of queries.
+int64_t serve_args(Args& a, const torch::Tensor& U, const torch::Tensor& V,
+                   const torch::Tensor& u_idx, const torch::Tensor& i_idx) {
+    a.tensor(U, kBF16, "U");
+    a.tensor(V, kBF16, "V");
+    a.tensor(u_idx, kI64, "u_idx");
+    TORCH_CHECK(U.dim() == 2 && V.dim() == 2, a.name(),
+                ": U and V must be 2-D");
+    TORCH_CHECK(U.size(1) == V.size(1), a.name(), ": U/V rank mismatch");
+    a.flat(i_idx, kI64, "i_idx", u_idx.numel(), /*exact=*/true);
+    return u_idx.numel();
 }
 
 void predict_dot(torch::Tensor U, torch::Tensor V, torch::Tensor u_idx,
                  torch::Tensor i_idx, torch::Tensor out, int64_t stream) {
-    check_t(U, torch::kBFloat16, "U");
-    check_t(V, torch::kBFloat16, "V");
-    check_t(u_idx, torch::kInt64, "u_idx");
-    check_t(i_idx, torch::kInt64, "i_idx");
-    check_t(out, torch::kFloat32, "out");
-    TORCH_CHECK(U.dim() == 2 && V.dim() == 2, "U and V must be 2-D");
-    TORCH_CHECK(U.size(1) == V.size(1), "rank mismatch");
-    TORCH_CHECK(i_idx.numel() == u_idx.numel(),
-                "u_idx and i_idx must have the same length");
-    TORCH_CHECK(out.numel() >= u_idx.numel(),
-                "out must have at least one element per query");
-    check_hip(fma_predict_dot(bf16_ptr(U), bf16_ptr(V),
-                              u_idx.data_ptr<int64_t>(),
-                              i_idx.data_ptr<int64_t>(),
-                              out.data_ptr<float>(), u_idx.numel(),
-                              (int)U.size(1), (void*)stream),
-              "predict_dot");
+    Args a("predict_dot");
+    const int64_t nq = serve_args(a, U, V, u_idx, i_idx);
+    a.flat(out, kF32, "out", nq, /*exact=*/false);
+    check_hip(fma_predict_dot(bf16(U), bf16(V), i64(u_idx), i64(i_idx),
+                              f32(out), nq, (int)U.size(1),
+                              a.stream(stream)),
+              a.name());
 }
 
 void sgd_update(torch::Tensor U, torch::Tensor V, torch::Tensor u_idx,
                 torch::Tensor i_idx, torch::Tensor r, torch::Tensor err_out,
                 double lr, double user_reg, double item_reg, int64_t stream) {
-    check_t(U, torch::kBFloat16, "U");
-    check_t(V, torch::kBFloat16, "V");
-    check_t(u_idx, torch::kInt64, "u_idx");
-    check_t(i_idx, torch::kInt64, "i_idx");
-    check_t(r, torch::kFloat32, "r");
-    float* ep = nullptr;
-    if (err_out.numel() > 0) {
-        check_t(err_out, torch::kFloat32, "err_out");
-        ep = err_out.data_ptr<float>();
-    }
-    const int64_t nq = u_idx.numel();
-    TORCH_CHECK(U.dim() == 2 && V.dim() == 2, "U and V must be 2-D");
-    TORCH_CHECK(U.size(1) == V.size(1), "rank mismatch");
-    TORCH_CHECK(i_idx.numel() == nq && r.numel() == nq,
-                "u_idx, i_idx and r must have the same length");
-    TORCH_CHECK(err_out.numel() == 0 || err_out.numel() >= nq,
-                "err_out must be empty or have one element per query");
-    check_hip(fma_sgd_update(bf16_ptr_mut(U), bf16_ptr_mut(V),
-                             u_idx.data_ptr<int64_t>(),
-                             i_idx.data_ptr<int64_t>(), r.data_ptr<float>(),
+    Args a("sgd_update");
+    const int64_t nq = serve_args(a, U, V, u_idx, i_idx);
+    a.flat(r, kF32, "r", nq, /*exact=*/true);
+    float* ep = a.optional(err_out, kF32, "err_out", nq) ? f32(err_out)
+                                                         : nullptr;
+    check_hip(fma_sgd_update(bf16(U), bf16(V), i64(u_idx), i64(i_idx), f32(r),
                              ep, nq, (int)U.size(1), (float)lr,
-                             (float)user_reg, (float)item_reg, (void*)stream),
-              "sgd_update");
+                             (float)user_reg, (float)item_reg,
+                             a.stream(stream)),
+              a.name());
 }
+
+// ------------------------------------------------- MFMA probes and dumps
 
 void mfma_probe_f32(torch::Tensor A, torch::Tensor B, torch::Tensor D,
                     int64_t stream) {
-    check_t(A, torch::kFloat32, "A");
-    check_t(B, torch::kFloat32, "B");
-    check_t(D, torch::kFloat32, "D");
-    check_hip(fma_mfma_probe_f32(A.data_ptr<float>(), B.data_ptr<float>(),
-                                 D.data_ptr<float>(), (void*)stream),
-              "mfma_probe_f32");
+    Args a("mfma_probe_f32");
+    a.flat(A, kF32, "A", 16 * 4, /*exact=*/true);
+    a.flat(B, kF32, "B", 4 * 16, true);
+    a.flat(D, kF32, "D", 16 * 16, true);
+    check_hip(fma_mfma_probe_f32(f32(A), f32(B), f32(D), a.stream(stream)),
+              a.name());
 }
 
 void mfma_probe_bf16(torch::Tensor Xt, torch::Tensor Yt, torch::Tensor C,
                      int64_t stream) {
-    check_t(Xt, torch::kBFloat16, "Xt");
-    check_t(Yt, torch::kBFloat16, "Yt");
-    check_t(C, torch::kFloat32, "C");
-    check_hip(fma_mfma_probe_bf16(bf16_ptr(Xt), bf16_ptr(Yt),
-                                  C.data_ptr<float>(), (void*)stream),
-              "mfma_probe_bf16");
+    Args a("mfma_probe_bf16");
+    a.flat(Xt, kBF16, "Xt", 32 * 16, /*exact=*/true);
+    a.flat(Yt, kBF16, "Yt", 32 * 16, true);
+    a.flat(C, kF32, "C", 16 * 16, true);
+    check_hip(fma_mfma_probe_bf16(bf16(Xt), bf16(Yt), f32(C),
+                                  a.stream(stream)),
+              a.name());
 }
 
 void mfma_probe_fp8(torch::Tensor Xt, torch::Tensor Yt, torch::Tensor C,
                     int64_t stream) {
-    check_t(Xt, torch::kUInt8, "Xt");
-    check_t(Yt, torch::kUInt8, "Yt");
-    check_t(C, torch::kFloat32, "C");
-    check_hip(fma_mfma_probe_fp8(fp8_ptr(Xt), fp8_ptr(Yt),
-                                 C.data_ptr<float>(), (void*)stream),
-              "mfma_probe_fp8");
+    Args a("mfma_probe_fp8");
+    a.flat(Xt, kU8, "Xt", 32 * 16, /*exact=*/true);
+    a.flat(Yt, kU8, "Yt", 32 * 16, true);
+    a.flat(C, kF32, "C", 16 * 16, true);
+    check_hip(fma_mfma_probe_fp8(u8(Xt), u8(Yt), f32(C), a.stream(stream)),
+              a.name());
 }
 
+// The dumps read entity 0 of the CSR (so it needs one) through the bf16
+// stage; ``out`` holds the [k+16][32] stage image.
 void dbg_stage_dump(torch::Tensor indptr, torch::Tensor indices,
                     torch::Tensor values, torch::Tensor factors,
                     torch::Tensor out, int64_t stream) {
-    check_hip(fma_dbg_stage_dump((int)factors.size(1),
-                                 indptr.data_ptr<int64_t>(),
-                                 indices.data_ptr<int>(),
-                                 values.data_ptr<float>(), bf16_ptr(factors),
-                                 bf16_ptr_mut(out), (void*)stream),
-              "dbg_stage_dump");
+    Args a("dbg_stage_dump");
+    TORCH_CHECK(a.csr(indptr, indices, values) >= 1, a.name(),
+                ": indptr must hold at least one entity");
+    const int k = a.factors(factors, /*fp8=*/false, "factors");
+    a.flat(out, kBF16, "out", (int64_t)(k + 16) * 32, /*exact=*/false);
+    check_hip(fma_dbg_stage_dump(k, i64(indptr), i32(indices), f32(values),
+                                 bf16(factors), bf16(out), a.stream(stream)),
+              a.name());
 }
 
+// ``out`` holds [4 waves][k/16 + 1 tiles][64 lanes][8] fragment elements.
 void dbg_frag_dump(torch::Tensor indptr, torch::Tensor indices,
                    torch::Tensor values, torch::Tensor factors,
                    torch::Tensor out, int64_t stream) {
-    check_hip(fma_dbg_frag_dump((int)factors.size(1),
-                                indptr.data_ptr<int64_t>(),
-                                indices.data_ptr<int>(),
-                                values.data_ptr<float>(), bf16_ptr(factors),
-                                bf16_ptr_mut(out), (void*)stream),
-              "dbg_frag_dump");
+    Args a("dbg_frag_dump");
+    TORCH_CHECK(a.csr(indptr, indices, values) >= 1, a.name(),
+                ": indptr must hold at least one entity");
+    const int k = a.factors(factors, /*fp8=*/false, "factors");
+    a.flat(out, kBF16, "out", (int64_t)4 * (k / 16 + 1) * 64 * 8,
+           /*exact=*/false);
+    check_hip(fma_dbg_frag_dump(k, i64(indptr), i32(indices), f32(values),
+                                bf16(factors), bf16(out), a.stream(stream)),
+              a.name());
 }
 
 void dbg_gramian(torch::Tensor indptr, torch::Tensor indices,
                  torch::Tensor values, torch::Tensor factors,
                  torch::Tensor A_out, torch::Tensor bhi, torch::Tensor blo,
                  double reg, int64_t stream) {
-    check_hip(fma_dbg_gramian((int)factors.size(1),
-                              indptr.data_ptr<int64_t>(),
-                              indices.data_ptr<int>(),
-                              values.data_ptr<float>(), bf16_ptr(factors),
-                              A_out.data_ptr<float>(), bhi.data_ptr<float>(),
-                              blo.data_ptr<float>(), indptr.size(0) - 1,
-                              (float)reg, (void*)stream),
-              "dbg_gramian");
+    Args a("dbg_gramian");
+    const int64_t nrows = a.csr(indptr, indices, values);
+    const int k = a.factors(factors, /*fp8=*/false, "factors");
+    a.square_rows(A_out, "A_out", nrows, k);
+    a.rows(bhi, kF32, "bhi", nrows, k);
+    a.rows(blo, kF32, "blo", nrows, k);
+    check_hip(fma_dbg_gramian(k, i64(indptr), i32(indices), f32(values),
+                              bf16(factors), f32(A_out), f32(bhi), f32(blo),
+                              nrows, (float)reg, a.stream(stream)),
+              a.name());
 }
 
 }  // namespace
@@ -711,20 +634,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     register_kvserver(m);
     m.def("als_solve_fused", &als_solve_fused);
     m.def("gramian", &gramian);
-    m.def("gramian_fp8", &gramian_fp8);
-    m.def("als_solve_fused_fp8", &als_solve_fused_fp8);
     m.attr("BROADCAST_SHFL") = kBroadcastShfl;
     m.attr("BROADCAST_DEFAULT") = kBroadcastDefault;
-    m.def("als_solve_wavefused", &als_solve_wavefused);
-    m.def("als_solve_wavefused", &als_solve_wavefused_v);
+    // ``variant`` is optional (positional or by name): BROADCAST_DEFAULT
+    m.def("als_solve_wavefused", &als_solve_wavefused, py::arg("indptr"),
+          py::arg("indices"), py::arg("values"), py::arg("factors"),
+          py::arg("out_f32"), py::arg("out_bf16"), py::arg("out_fp8"),
+          py::arg("row_order"), py::arg("reg"), py::arg("stream"),
+          py::arg("variant") = kBroadcastDefault);
+    m.def("als_solve_wavefused_db", &als_solve_wavefused_db,
+          py::arg("indptr"), py::arg("indices"), py::arg("values"),
+          py::arg("factors"), py::arg("out_f32"), py::arg("out_bf16"),
+          py::arg("out_fp8"), py::arg("row_order"), py::arg("reg"),
+          py::arg("stream"), py::arg("variant") = kBroadcastDefault);
     m.def("als_solve_wavefused2", &als_solve_wavefused2);
-    m.def("als_solve_wavefused_db", &als_solve_wavefused_db);
-    m.def("als_solve_wavefused_db", &als_solve_wavefused_db_v);
     m.def("cholesky_solve", &cholesky_solve);
     m.def("cholesky_solve_ph", &cholesky_solve_ph);
     m.def("ldl_solve_wave", &ldl_solve_wave);
-    m.def("ldl_solve_wave_reg", &ldl_solve_wave_reg);
-    m.def("ldl_solve_wave_reg", &ldl_solve_wave_reg_v);
+    m.def("ldl_solve_wave_reg", &ldl_solve_wave_reg, py::arg("A"),
+          py::arg("b"), py::arg("x"), py::arg("x_bf16"), py::arg("x_fp8"),
+          py::arg("stream"), py::arg("variant") = kBroadcastDefault);
     m.def("sdca_pass", &sdca_pass);
     m.def("sdca_num_waves", &sdca_num_waves);
     m.def("svm_margins", &svm_margins);

@@ -6,6 +6,7 @@
 
 // re-instantiate the geometry/device functions
 #include "als_kernels_device.inc"
+#include "fma_api.h"
 
 // Dump the staged Gt LDS image (one chunk): out[(K+16)][32] bf16.
 template <int KT>
@@ -87,29 +88,42 @@ __global__ void k_gramian_dbg(const long long* __restrict__ indptr,
     }
 }
 
-extern "C" hipError_t fma_dbg_stage_dump(
+// bf16 gathers only; k = 16..128
+
+extern "C" int fma_dbg_stage_dump(
     int k, const long long* indptr, const int* indices, const float* values,
-    const unsigned short* factors, unsigned short* out, hipStream_t stream) {
-    DISPATCH_KT(k, (k_stage_dump<KT><<<dim3(1), dim3(256), 0, stream>>>(
-        indptr, indices, values, factors, out)));
-    return hipGetLastError();
+    const unsigned short* factors, unsigned short* out, void* stream) {
+    if (k % 16) return hipErrorInvalidValue;
+    return dispatch_ic<1, 2, 3, 4, 5, 6, 7, 8>(k / 16, [&](auto kt) {
+        k_stage_dump<decltype(kt)::value>
+            <<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>(
+                indptr, indices, values, factors, out);
+        return hipGetLastError();
+    });
 }
 
-extern "C" hipError_t fma_dbg_frag_dump(
+extern "C" int fma_dbg_frag_dump(
     int k, const long long* indptr, const int* indices, const float* values,
-    const unsigned short* factors, unsigned short* out, hipStream_t stream) {
-    DISPATCH_KT(k, (k_frag_dump<KT><<<dim3(1), dim3(256), 0, stream>>>(
-        indptr, indices, values, factors, out)));
-    return hipGetLastError();
+    const unsigned short* factors, unsigned short* out, void* stream) {
+    if (k % 16) return hipErrorInvalidValue;
+    return dispatch_ic<1, 2, 3, 4, 5, 6, 7, 8>(k / 16, [&](auto kt) {
+        k_frag_dump<decltype(kt)::value>
+            <<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>(
+                indptr, indices, values, factors, out);
+        return hipGetLastError();
+    });
 }
 
-extern "C" hipError_t fma_dbg_gramian(
+extern "C" int fma_dbg_gramian(
     int k, const long long* indptr, const int* indices, const float* values,
     const unsigned short* factors, float* A_out, float* bhi_out,
-    float* blo_out, long long nrows, float reg, hipStream_t stream) {
-    DISPATCH_KT(k, (k_gramian_dbg<KT><<<dim3((unsigned)nrows), dim3(256), 0,
-                                        stream>>>(
-        indptr, indices, values, factors, A_out, bhi_out, blo_out, nrows,
-        reg)));
-    return hipGetLastError();
+    float* blo_out, long long nrows, float reg, void* stream) {
+    if (k % 16 || nrows <= 0) return hipErrorInvalidValue;
+    return dispatch_ic<1, 2, 3, 4, 5, 6, 7, 8>(k / 16, [&](auto kt) {
+        k_gramian_dbg<decltype(kt)::value>
+            <<<dim3((unsigned)nrows), dim3(256), 0, (hipStream_t)stream>>>(
+                indptr, indices, values, factors, A_out, bhi_out, blo_out,
+                nrows, reg);
+        return hipGetLastError();
+    });
 }

@@ -1,0 +1,115 @@
+// The C ABI between the HIP translation units and bindings.cpp, declared
+// once.  The .hip files include this header and DEFINE every entry point
+// with exactly these signatures (a drifted argument list fails to compile
+// there); bindings.cpp includes it and calls them.  Deliberately free of
+// HIP and torch headers so both sides can see it:
+//   status   int     (a hipError_t value; 0 = success, fma_err_str names it)
+//   stream   void*   (a hipStream_t)
+//   bf16     unsigned short words, e4m3 unsigned char bytes
+//   int64    long long
+// Optional pointers (row_order, the low-precision output images, perm,
+// err_out) may be null.  Launchers validate k and nrows only; everything
+// about the tensors behind the pointers is the binding's job.
+#pragma once
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+const char* fma_err_str(int err);
+
+// ---- ALS, block path (k = 16..128): als_kernels.hip
+// fp8 != 0: factors are e4m3 bytes and the low-precision image written is
+// out_fp8; else bf16 words and out_bf16.  The other image must be null.
+int fma_als_solve_fused(int k, int fp8, const long long* indptr,
+                        const int* indices, const float* values,
+                        const void* factors, float* out_f32,
+                        unsigned short* out_bf16, unsigned char* out_fp8,
+                        const int* row_order, long long nrows, float reg,
+                        void* stream);
+int fma_gramian(int k, int fp8, const long long* indptr, const int* indices,
+                const float* values, const void* factors, float* A_out,
+                float* b_out, const int* row_order, long long nrows,
+                float reg, void* stream);
+// phases bitmask: 1 = eliminate, 2 = substitute
+int fma_cholesky_solve_ph(int k, const float* A_in, const float* b_in,
+                          float* x_out, long long nrows, int phases,
+                          void* stream);
+int fma_cholesky_solve(int k, const float* A_in, const float* b_in,
+                       float* x_out, long long nrows, void* stream);
+
+// ---- ALS, wave path (k = 16..64).  variant: a WREG_BC_* broadcast level
+// (0..3; the _reg and _db kernels exist for 0 and 3 only)
+int fma_ldl_solve_wave(int k, const float* A_in, const float* b_in,
+                       float* x_out, unsigned short* x_bf16,
+                       unsigned char* x_fp8, long long nrows, void* stream);
+int fma_ldl_solve_wave_reg(int k, const float* A_in, const float* b_in,
+                           float* x_out, unsigned short* x_bf16,
+                           unsigned char* x_fp8, long long nrows, int variant,
+                           void* stream);
+int fma_als_solve_wavefused(int k, int fp8, const long long* indptr,
+                            const int* indices, const float* values,
+                            const void* factors, float* out_f32,
+                            unsigned short* out_bf16, unsigned char* out_fp8,
+                            const int* row_order, long long nrows, float reg,
+                            int variant, void* stream);
+// e4m3 factors only
+int fma_als_solve_wavefused_db(int k, const long long* indptr,
+                               const int* indices, const float* values,
+                               const void* factors, float* out_f32,
+                               unsigned short* out_bf16,
+                               unsigned char* out_fp8, const int* row_order,
+                               long long nrows, float reg, int variant,
+                               void* stream);
+// ---- ALS, wave-quad path (k = 80..128, e4m3 factors only)
+int fma_als_solve_wavefused2(int k, const long long* indptr,
+                             const int* indices, const float* values,
+                             const unsigned char* factors, float* out_f32,
+                             unsigned char* out_fp8, const int* row_order,
+                             long long nrows, float reg, void* stream);
+
+// ---- MFMA layout probes: fixed-size operands (als_kernels.hip)
+int fma_mfma_probe_f32(const float* A /*[16][4]*/, const float* B /*[4][16]*/,
+                       float* D /*[16][16]*/, void* stream);
+int fma_mfma_probe_bf16(const unsigned short* Xt /*[32][16]*/,
+                        const unsigned short* Yt /*[32][16]*/,
+                        float* C /*[16][16]*/, void* stream);
+int fma_mfma_probe_fp8(const unsigned char* Xt /*[32][16]*/,
+                       const unsigned char* Yt /*[32][16]*/,
+                       float* C /*[16][16]*/, void* stream);
+
+// ---- bring-up dumps of entity 0 / the split b columns: debug_kernels.hip
+int fma_dbg_stage_dump(int k, const long long* indptr, const int* indices,
+                       const float* values, const unsigned short* factors,
+                       unsigned short* out /*[k+16][32]*/, void* stream);
+int fma_dbg_frag_dump(int k, const long long* indptr, const int* indices,
+                      const float* values, const unsigned short* factors,
+                      unsigned short* out /*[4][k/16+1][64][8]*/,
+                      void* stream);
+int fma_dbg_gramian(int k, const long long* indptr, const int* indices,
+                    const float* values, const unsigned short* factors,
+                    float* A_out, float* bhi_out, float* blo_out,
+                    long long nrows, float reg, void* stream);
+
+// ---- SVM: svm_kernels.hip
+int fma_sdca_pass(const long long* indptr, const int* indices,
+                  const float* values, const float* y, const float* norms_sq,
+                  const int* perm, float* alpha, float* v, long long nrows,
+                  float scale, void* stream);
+long long fma_sdca_num_waves(long long nrows);
+int fma_svm_margins(const long long* indptr, const int* indices,
+                    const float* values, const float* w, float* out,
+                    long long nrows, void* stream);
+
+// ---- serving: serve_kernels.hip
+int fma_predict_dot(const unsigned short* U, const unsigned short* V,
+                    const long long* u_idx, const long long* i_idx,
+                    float* out, long long nq, int k, void* stream);
+int fma_sgd_update(unsigned short* U, unsigned short* V,
+                   const long long* u_idx, const long long* i_idx,
+                   const float* r, float* err_out, long long nq, int k,
+                   float lr, float user_reg, float item_reg, void* stream);
+
+#ifdef __cplusplus
+}
+#endif

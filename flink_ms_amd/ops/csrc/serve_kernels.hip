@@ -9,6 +9,7 @@
 // One wave per query; factors are bf16 rows of the store, math in fp32.
 
 #include "common.hip.h"
+#include "fma_api.h"
 
 __launch_bounds__(256)
 __global__ void k_predict_dot(const unsigned short* __restrict__ U,
@@ -70,26 +71,26 @@ __global__ void k_sgd_update(unsigned short* __restrict__ U,
     }
 }
 
-extern "C" hipError_t fma_predict_dot(
+extern "C" int fma_predict_dot(
     const unsigned short* U, const unsigned short* V, const long long* u_idx,
     const long long* i_idx, float* out, long long nq, int k,
-    hipStream_t stream) {
+    void* stream) {
     if (nq <= 0 || k <= 0 || k > 128) return hipErrorInvalidValue;
     long long waves = (nq + 3) / 4;
     unsigned grid = (unsigned)(waves < 2048 ? waves : 2048);
-    k_predict_dot<<<dim3(grid), dim3(256), 0, stream>>>(
+    k_predict_dot<<<dim3(grid), dim3(256), 0, (hipStream_t)stream>>>(
         U, V, u_idx, i_idx, out, nq, k);
     return hipGetLastError();
 }
 
-extern "C" hipError_t fma_sgd_update(
+extern "C" int fma_sgd_update(
     unsigned short* U, unsigned short* V, const long long* u_idx,
     const long long* i_idx, const float* r, float* err_out, long long nq,
-    int k, float lr, float user_reg, float item_reg, hipStream_t stream) {
+    int k, float lr, float user_reg, float item_reg, void* stream) {
     if (nq <= 0 || k <= 0 || k > 128) return hipErrorInvalidValue;
     long long waves = (nq + 3) / 4;
     unsigned grid = (unsigned)(waves < 2048 ? waves : 2048);
-    k_sgd_update<<<dim3(grid), dim3(256), 0, stream>>>(
+    k_sgd_update<<<dim3(grid), dim3(256), 0, (hipStream_t)stream>>>(
         U, V, u_idx, i_idx, r, err_out, nq, k, lr, user_reg, item_reg);
     return hipGetLastError();
 }

@@ -19,6 +19,7 @@
 // deltas) runs as an RCCL all-reduce in flink_ms_amd/parallel/.
 
 #include "common.hip.h"
+#include "fma_api.h"
 
 __launch_bounds__(256)
 __global__ void k_sdca_pass(const long long* __restrict__ indptr,
@@ -118,24 +119,24 @@ extern "C" long long fma_sdca_num_waves(long long nrows) {
     return nrows <= 0 ? 0 : (long long)sdca_grid(nrows) * 4;
 }
 
-extern "C" hipError_t fma_sdca_pass(
+extern "C" int fma_sdca_pass(
     const long long* indptr, const int* indices, const float* values,
     const float* y, const float* norms_sq, const int* perm, float* alpha,
-    float* v, long long nrows, float scale, hipStream_t stream) {
+    float* v, long long nrows, float scale, void* stream) {
     if (nrows <= 0) return hipErrorInvalidValue;
     const unsigned grid = sdca_grid(nrows);
-    k_sdca_pass<<<dim3(grid), dim3(256), 0, stream>>>(
+    k_sdca_pass<<<dim3(grid), dim3(256), 0, (hipStream_t)stream>>>(
         indptr, indices, values, y, norms_sq, perm, alpha, v, nrows, scale);
     return hipGetLastError();
 }
 
-extern "C" hipError_t fma_svm_margins(
+extern "C" int fma_svm_margins(
     const long long* indptr, const int* indices, const float* values,
-    const float* w, float* out, long long nrows, hipStream_t stream) {
+    const float* w, float* out, long long nrows, void* stream) {
     if (nrows <= 0) return hipErrorInvalidValue;
     long long waves = (nrows + 3) / 4;
     unsigned grid = (unsigned)(waves < 2048 ? waves : 2048);
-    k_svm_margins<<<dim3(grid), dim3(256), 0, stream>>>(
+    k_svm_margins<<<dim3(grid), dim3(256), 0, (hipStream_t)stream>>>(
         indptr, indices, values, w, out, nrows);
     return hipGetLastError();
 }

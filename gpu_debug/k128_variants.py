@@ -1,7 +1,7 @@
 """Time the k=128 half-iteration variants on the 1B-config user shard.
 
 Variants: wave-quad fused (wavefused2), block-fused fp8, modular fp8
-(gramian_fp8 -> k_cholesky_solve, slabbed).  Run on a GPU box:
+(k_gramian<KT, true> -> k_cholesky_solve, slabbed).  Run on a GPU box:
     python gpu_debug/k128_variants.py [--ratings N] [--users N] [--items N]
 """
 import argparse

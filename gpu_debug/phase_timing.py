@@ -46,7 +46,7 @@ b = torch.empty(csr.num_rows, k, dtype=torch.float32, device=dev)
 x = torch.empty(csr.num_rows, k, dtype=torch.float32, device=dev)
 
 timeit("user fused (gramian+chol)", lambda: hip.als_solve_fused(
-    csr.indptr, csr.indices, csr.values, V, out, emptyb, emptyi, 0.9, st()))
+    csr.indptr, csr.indices, csr.values, V, out, emptyb, emptyb, emptyi, 0.9, st()))
 timeit("user gramian only", lambda: hip.gramian(
     csr.indptr, csr.indices, csr.values, V, A, b, _e8, 0.9, st()))
 timeit("user cholesky only", lambda: hip.cholesky_solve(A, b, x, st()))
@@ -55,14 +55,14 @@ outi = torch.empty(icsr.num_rows, k, dtype=torch.float32, device=dev)
 Ai = torch.empty(icsr.num_rows, k, k, dtype=torch.float32, device=dev)
 bi = torch.empty(icsr.num_rows, k, dtype=torch.float32, device=dev)
 timeit("item fused", lambda: hip.als_solve_fused(
-    icsr.indptr, icsr.indices, icsr.values, U, outi, emptyb, emptyi, 0.9, st()))
+    icsr.indptr, icsr.indices, icsr.values, U, outi, emptyb, emptyb, emptyi, 0.9, st()))
 timeit("item gramian only", lambda: hip.gramian(
     icsr.indptr, icsr.indices, icsr.values, U, Ai, bi, _e8, 0.9, st()))
 
 # row_order effect
 order = torch.argsort(csr.row_counts(), descending=True).to(torch.int32).to(dev)
 timeit("user fused + degree order", lambda: hip.als_solve_fused(
-    csr.indptr, csr.indices, csr.values, V, out, emptyb, order, 0.9, st()))
+    csr.indptr, csr.indices, csr.values, V, out, emptyb, emptyb, order, 0.9, st()))
 
 # --- phase ablation on the standalone solver ---
 timeit("chol load-only (phases=0)", lambda: hip.cholesky_solve_ph(A, b, x, 0, st()))

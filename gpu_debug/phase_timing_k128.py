@@ -49,5 +49,5 @@ timeit("full user side (als_solve_side)", lambda: ops.als_solve_side(
 out_full = torch.empty(csr.num_rows, k, dtype=torch.float32, device=dev)
 emptyi = torch.empty(0, dtype=torch.int32, device=dev)
 timeit("full user side FUSED kernel", lambda: hip.als_solve_fused(
-    csr.indptr, csr.indices, csr.values, V, out_full, emptyb, emptyi,
-    0.9, st()), reps=2)
+    csr.indptr, csr.indices, csr.values, V, out_full, emptyb, emptyb,
+    emptyi, 0.9, st()), reps=2)
