@@ -11,6 +11,7 @@ Reference job -> command (``python -m flink_ms_amd.cli.<name> --flags``):
   SVMKafkaProducer.java    -> producer --model svm
   ALS/SVMKafkaConsumer     -> serve           (the serving job)
   ALSPredict.java          -> als_predict     (interactive)
+  (no reference analog)    -> als_recommend   (interactive top-N)
   SVMPredict.java          -> svm_predict     (interactive)
   ALSPredictRandom.java    -> als_predict_random
   SVMPredictRandom.java    -> svm_predict_random

@@ -376,6 +376,66 @@ def predict_dot(U: torch.Tensor, V: torch.Tensor, u_idx: torch.Tensor,
     return reference.predict_dot_reference(U, V, u_idx, i_idx)
 
 
+def topk_scores(Q: torch.Tensor, V: torch.Tensor, topk: int,
+                cand: Optional[torch.Tensor] = None,
+                exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                chunk_items: Optional[int] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-N recommendations: for every query row of ``Q`` [nq, k] the
+    ``topk`` best rows of ``V`` [nv, k] by dot product, fused score +
+    selection on the GPU (the [nq, nv] score matrix is never materialized).
+
+    ``cand``: int64 rows of V to consider (``None`` = all).  ``exclude`` =
+    ``(excl_ptr [nq + 1], excl_rows)``: per query an ascending slice of V
+    rows never to return.  ``chunk_items`` overrides the launcher's split
+    of the candidates (tests; the result does not depend on it).
+
+    Returns (scores fp32 [nq, topk], rows int64 [nq, topk]): score
+    descending, lower row first among equal scores, NaN scores last, short
+    results padded with row -1 / score -inf."""
+    topk = int(topk)
+    if not 1 <= topk <= 128:
+        raise ValueError(f"topk must be in 1..128, got {topk}")
+    if Q.dim() != 2 or V.dim() != 2 or Q.shape[1] != V.shape[1]:
+        raise ValueError("Q and V must be 2-D with one rank")
+    nq, nv = Q.shape[0], V.shape[0]
+    if cand is not None:
+        cand = cand.long().contiguous()
+        if cand.dim() != 1 or cand.numel() == 0:
+            raise ValueError("cand must be 1-D and non-empty")
+        if int(cand.min()) < 0 or int(cand.max()) >= nv:
+            raise ValueError(f"cand entries must be rows of V (0..{nv - 1})")
+    if exclude is not None:
+        ptr, ex = exclude
+        ptr = ptr.long().contiguous()
+        ex = ex.long().contiguous()
+        if ptr.dim() != 1 or ptr.numel() != nq + 1 or ex.dim() != 1:
+            raise ValueError("exclude must be (excl_ptr [nq + 1], excl_rows)")
+        if (int(ptr[0]) < 0 or int(ptr[-1]) > ex.numel()
+                or bool((ptr[1:] < ptr[:-1]).any())):
+            raise ValueError("excl_ptr must be non-decreasing offsets into "
+                             "excl_rows")
+        exclude = (ptr, ex)
+    if Q.is_cuda:
+        ops = _require_hip()
+        none = _empty(Q.device)
+        ptr, ex = exclude if exclude is not None else (none, none)
+        return tuple(ops.topk_scores(
+            Q.to(torch.bfloat16).contiguous(),
+            V.to(torch.bfloat16).contiguous(),
+            cand.to(Q.device) if cand is not None else none,
+            ptr.to(Q.device), ex.to(Q.device), topk,
+            int(chunk_items or 0), _stream()))
+    return reference.topk_scores_reference(Q, V, topk, cand, exclude)
+
+
+def topk_chunk_items(nq: int, nc: int, topk: int) -> int:
+    """Candidates per chunk that a GPU ``topk_scores`` over ``nq`` queries
+    and ``nc`` candidates uses when ``chunk_items`` is not given: one wave
+    scores one (16-query tile, chunk) pair."""
+    return int(_require_hip().topk_chunk_items(int(nq), int(nc), int(topk)))
+
+
 def sgd_update(U: torch.Tensor, V: torch.Tensor, u_idx: torch.Tensor,
                i_idx: torch.Tensor, r: torch.Tensor, lr: float,
                user_reg: float, item_reg: float) -> torch.Tensor:

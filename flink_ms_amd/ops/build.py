@@ -26,7 +26,7 @@ SO_PATH = PKG_DIR / "_hip_ops.so"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 KERNEL_SOURCES = ["als_kernels.hip", "svm_kernels.hip", "serve_kernels.hip",
-                  "debug_kernels.hip"]
+                  "debug_kernels.hip", "topk_kernels.hip"]
 KVSERVER_SRC = "kvserver.cpp"  # serving/csrc: host-only C++ (Netty parity)
 
 

@@ -546,6 +546,80 @@ void sgd_update(torch::Tensor U, torch::Tensor V, torch::Tensor u_idx,
               a.name());
 }
 
+// Top-N: Q bf16 [nq][k] queries against the cand rows (empty = all) of V
+// bf16 [nv][k]; excl_ptr [nq+1] / excl_rows (both empty = none) are the
+// per-query sorted exclusion slices.  Returns (scores fp32 [nq][topk],
+// rows int64 [nq][topk]).  The CONTENTS of cand and excl_ptr index device
+// memory and are range-checked by the Python wrapper (ops.topk_scores),
+// which is the only caller; this binding checks metadata.
+py::tuple topk_scores(torch::Tensor Q, torch::Tensor V, torch::Tensor cand,
+                      torch::Tensor excl_ptr, torch::Tensor excl_rows,
+                      int64_t topk, int64_t chunk_items, int64_t stream) {
+    Args a("topk_scores");
+    a.tensor(Q, kBF16, "Q");
+    a.tensor(V, kBF16, "V");
+    TORCH_CHECK(Q.dim() == 2 && V.dim() == 2, a.name(),
+                ": Q and V must be 2-D");
+    TORCH_CHECK(Q.size(1) == V.size(1), a.name(), ": Q/V rank mismatch");
+    const int64_t nq = Q.size(0), nv = V.size(0), k = Q.size(1);
+    TORCH_CHECK(nq >= 1 && nv >= 1, a.name(),
+                ": Q and V must have at least one row");
+    TORCH_CHECK(k >= 1 && k <= 128, a.name(), ": rank k = ", k,
+                " must be in 1..128");
+    TORCH_CHECK(topk >= 1 && topk <= 128, a.name(), ": topk = ", topk,
+                " must be in 1..128");
+    TORCH_CHECK(chunk_items >= 0, a.name(),
+                ": chunk_items must be >= 0 (0 = the launcher's choice)");
+    const long long* candp = nullptr;
+    int64_t nc = nv;
+    if (a.optional(cand, kI64, "cand", 1)) {
+        TORCH_CHECK(cand.dim() == 1, a.name(), ": cand must be 1-D");
+        candp = i64(cand);
+        nc = cand.numel();
+    }
+    TORCH_CHECK(nv < (int64_t(1) << 31) && nc < (int64_t(1) << 31), a.name(),
+                ": V and cand must have fewer than 2^31 rows");
+    const long long* eptr = nullptr;
+    const long long* erows = nullptr;
+    if (a.optional(excl_ptr, kI64, "excl_ptr", 1)) {
+        TORCH_CHECK(excl_ptr.dim() == 1 && excl_ptr.numel() == nq + 1,
+                    a.name(), ": excl_ptr must be 1-D with nq + 1 = ", nq + 1,
+                    " elements, got ", excl_ptr.numel());
+        eptr = i64(excl_ptr);
+        if (a.optional(excl_rows, kI64, "excl_rows", 1)) {
+            TORCH_CHECK(excl_rows.dim() == 1, a.name(),
+                        ": excl_rows must be 1-D");
+            erows = i64(excl_rows);
+        }
+    } else {
+        TORCH_CHECK(excl_rows.numel() == 0, a.name(),
+                    ": excl_rows given without excl_ptr");
+    }
+    void* st = a.stream(stream);   // device check, before any allocation
+    const long long ws_bytes =
+        fma_topk_workspace_bytes(nq, nc, (int)topk, chunk_items);
+    TORCH_CHECK(ws_bytes >= 0, a.name(), ": bad shape");
+    auto opts = Q.options();
+    auto ws = torch::empty({(ws_bytes + 7) / 8}, opts.dtype(kI64));
+    auto scores = torch::empty({nq, topk}, opts.dtype(kF32));
+    auto rows = torch::empty({nq, topk}, opts.dtype(kI64));
+    check_hip(fma_topk_scores(bf16(Q), bf16(V), candp, eptr, erows,
+                              f32(scores), (long long*)rows.data_ptr(),
+                              ws.data_ptr(), ws_bytes, nq, nv, nc, (int)k,
+                              (int)topk, chunk_items, st),
+              a.name());
+    return py::make_tuple(scores, rows);
+}
+
+// Chunk length topk_scores uses for chunk_items = 0; host-only.
+int64_t topk_chunk_items(int64_t nq, int64_t nc, int64_t topk) {
+    TORCH_CHECK(topk >= 1 && topk <= 128 && nq >= 1 && nc >= 1 &&
+                    nc < (int64_t(1) << 31),
+                "topk_chunk_items: need nq, nc >= 1, nc < 2^31 and topk in "
+                "1..128");
+    return (int64_t)fma_topk_chunk_items(nq, nc, (int)topk);
+}
+
 // ------------------------------------------------- MFMA probes and dumps
 
 void mfma_probe_f32(torch::Tensor A, torch::Tensor B, torch::Tensor D,
@@ -659,6 +733,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("svm_margins", &svm_margins);
     m.def("predict_dot", &predict_dot);
     m.def("sgd_update", &sgd_update);
+    m.def("topk_scores", &topk_scores, py::arg("Q"), py::arg("V"),
+          py::arg("cand"), py::arg("excl_ptr"), py::arg("excl_rows"),
+          py::arg("topk"), py::arg("chunk_items"), py::arg("stream"));
+    m.def("topk_chunk_items", &topk_chunk_items);
     m.def("dbg_stage_dump", &dbg_stage_dump);
     m.def("dbg_frag_dump", &dbg_frag_dump);
     m.def("dbg_gramian", &dbg_gramian);

@@ -110,6 +110,31 @@ int fma_sgd_update(unsigned short* U, unsigned short* V,
                    const float* r, float* err_out, long long nq, int k,
                    float lr, float user_reg, float item_reg, void* stream);
 
+// ---- top-N recommendations: topk_kernels.hip
+// For each of the nq bf16 query rows of Q [nq][k]: the topk best of the nc
+// candidate rows of V [nv][k] (cand, or null = rows 0..nv-1, then nc == nv)
+// by fp32 dot, score descending and lower row of V first among equal
+// scores; NaN scores last; short results padded with row -1 / score -inf.
+// excl_ptr [nq+1] / excl_rows (both null = no exclusions): per query an
+// ascending slice of rows of V that must not be returned.  chunk_items = 0
+// lets the launcher choose (fma_topk_chunk_items); the result does not
+// depend on it.  The launcher validates 1 <= k, topk <= 128, nq, nc >= 1,
+// nv and nc < 2^31 and the workspace size (fma_topk_workspace_bytes, 8-byte
+// aligned).  It reads V at every cand entry and excl_rows at every excl_ptr
+// entry without a check: 0 <= cand < nv and 0 <= excl_ptr, non-decreasing,
+// <= the length of excl_rows are the PYTHON WRAPPER's job (ops.topk_scores),
+// not the binding's.  The two size helpers return -1 for a bad shape.
+int fma_topk_scores(const unsigned short* Q, const unsigned short* V,
+                    const long long* cand, const long long* excl_ptr,
+                    const long long* excl_rows, float* out_scores,
+                    long long* out_rows, void* workspace,
+                    long long workspace_bytes, long long nq, long long nv,
+                    long long nc, int k, int topk, long long chunk_items,
+                    void* stream);
+long long fma_topk_workspace_bytes(long long nq, long long nc, int topk,
+                                   long long chunk_items);
+long long fma_topk_chunk_items(long long nq, long long nc, int topk);
+
 #ifdef __cplusplus
 }
 #endif

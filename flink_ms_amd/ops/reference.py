@@ -283,3 +283,65 @@ def predict_dot_reference(
     p = user_factors[u_idx.long()].to(torch.float32)
     q = item_factors[i_idx.long()].to(torch.float32)
     return (p * q).sum(dim=-1)
+
+
+# ------------------------------------------------------------------ top-N
+
+def _topk_scores(Q, V, topk, cand, exclude, dtype):
+    nq = Q.shape[0]
+    rows = (torch.arange(V.shape[0], dtype=torch.int64) if cand is None
+            else cand.long().cpu())
+    # candidates in ascending row order: every later sort is stable, so
+    # equal scores keep it ("lower row of V first")
+    rows = rows[torch.argsort(rows, stable=True)]
+    S = Q.to(dtype).cpu() @ V.cpu()[rows].to(dtype).T          # [nq, nc]
+    nan = torch.isnan(S)
+    dead = torch.zeros_like(nan)
+    if exclude is not None:
+        ptr, ex = exclude
+        ptr = ptr.long().cpu()
+        ex = ex.long().cpu()
+        for q in range(nq):
+            dead[q] = torch.isin(rows, ex[int(ptr[q]):int(ptr[q + 1])])
+    order = torch.sort(torch.where(nan, torch.full_like(S, -torch.inf), S),
+                       dim=1, descending=True, stable=True).indices
+    # numbers, then NaN scores, then excluded rows
+    cls = (nan.to(torch.int8) + 2 * dead.to(torch.int8)).clamp_(max=2)
+    order = order.gather(
+        1, torch.sort(cls.gather(1, order), dim=1, stable=True).indices)
+    out_s = torch.full((nq, topk), -torch.inf, dtype=dtype)
+    out_r = torch.full((nq, topk), -1, dtype=torch.int64)
+    n = min(topk, rows.numel())
+    head = order[:, :n]
+    live = ~dead.gather(1, head)
+    out_s[:, :n] = torch.where(live, S.gather(1, head), out_s[:, :n])
+    out_r[:, :n] = torch.where(live, rows[head], out_r[:, :n])
+    return out_s, out_r
+
+
+def topk_scores_reference(
+    Q: torch.Tensor,
+    V: torch.Tensor,
+    topk: int,
+    cand: Optional[torch.Tensor] = None,
+    exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-N by ``score(q, r) = dot(Q[q], V[r])`` in fp32 over the rows
+    ``cand`` of V (``None`` = all rows), without the rows
+    ``excl_rows[excl_ptr[q]:excl_ptr[q+1]]`` of ``exclude = (excl_ptr,
+    excl_rows)``.  Order: score descending, lower row first among equal
+    scores, NaN scores after every number.  Returns (scores [nq, topk],
+    rows int64 [nq, topk]); short results end in row -1 / score -inf."""
+    return _topk_scores(Q, V, int(topk), cand, exclude, torch.float32)
+
+
+def topk_scores_f64(
+    Q: torch.Tensor,
+    V: torch.Tensor,
+    topk: int,
+    cand: Optional[torch.Tensor] = None,
+    exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Float64 oracle of :func:`topk_scores_reference` (same contract,
+    scores in float64; bf16/fp32 inputs are exact in it)."""
+    return _topk_scores(Q, V, int(topk), cand, exclude, torch.float64)

@@ -10,6 +10,7 @@ server fronting the in-process stores:
   POST /model/{als|svm}/rows        ingest model text rows (producer path)
   POST /model/{als|svm}/load        ingest from files on disk
   GET  /als/predict?user=&item=     ALSPredict semantics
+  POST /als/recommend               top-n items per user (fused GPU top-k)
   POST /svm/predict                 SVMPredict / RangePartitionSVMPredict
   POST /sgd/update                  online SGD v1 step(s), SGD.java semantics
   POST /mse                         batch MSE over rating triples
@@ -56,6 +57,12 @@ class SVMPredictBody(BaseModel):
 class PredictBatchBody(BaseModel):
     users: List[str]
     items: List[str]
+
+
+class RecommendBody(BaseModel):
+    users: List[str]
+    n: int = 10
+    exclude: Optional[List[List[str]]] = None   # item ids, one list per user
 
 
 class SGDBody(BaseModel):
@@ -314,6 +321,25 @@ def create_app(als_store: Optional[ALSModelStore] = None,
             raise HTTPException(400, "users/items length mismatch")
         preds, ok = als.predict_batch(body.users, body.items)
         return {"predictions": preds.tolist(), "found": ok.tolist()}
+
+    @app.post("/als/recommend")
+    def als_recommend(body: RecommendBody):
+        """Top-n items per user over every live item of the store (fused
+        score + top-k kernel; no reference analog).  Ids are normalised as
+        in /als/predict; unknown users come back ``found`` False."""
+        if not 1 <= body.n <= 128:
+            raise HTTPException(400, "n must be in 1..128")
+        if body.exclude is not None and len(body.exclude) != len(body.users):
+            raise HTTPException(400, "users/exclude length mismatch")
+
+        def norm(s: str) -> str:
+            return s.strip().upper()
+
+        exclude = (None if body.exclude is None else
+                   [[norm(i) for i in ids] for ids in body.exclude])
+        found, items, scores = als.recommend(
+            [norm(u) for u in body.users], body.n, exclude)
+        return {"found": found, "items": items, "scores": scores}
 
     @app.post("/svm/predict")
     def svm_predict(body: SVMPredictBody):

@@ -37,6 +37,18 @@ class QueryClientHelper:
         r.raise_for_status()
         return r.json()
 
+    def als_recommend(self, users: List[str], n: int = 10,
+                      exclude: Optional[List[List[str]]] = None) -> dict:
+        """Top-``n`` items per user (/als/recommend): ``{"found", "items",
+        "scores"}``, one entry per user; ``exclude[i]`` lists item ids user
+        ``i`` must not get."""
+        payload: dict = {"users": users, "n": n}
+        if exclude is not None:
+            payload["exclude"] = exclude
+        r = self._client.post(f"{self.base}/als/recommend", json=payload)
+        r.raise_for_status()
+        return r.json()
+
     def svm_predict(self, vector: str, output_decision_function: bool = False,
                     threshold_value: float = 0.0,
                     range_size: Optional[int] = None) -> dict:

@@ -183,6 +183,9 @@ class ALSModelStore:
         self._k: Optional[int] = None
         self._blocks: Optional[FactorBlocks] = None  # attach + bulk ingest
         self._fmt = None
+        # recommend(): candidate item rows per source, cached per version
+        self._cand_version = 0     # bumped whenever a key gains a new row
+        self._cand_cache: Optional[tuple] = None
 
     # ------------------------------------------------------------ ingest
 
@@ -251,6 +254,7 @@ class ALSModelStore:
                                        offs[sel], lens[sel],
                                        keep_host=False)
                 n += cnt
+            self._cand_version += 1
             if n and self._payload:
                 for kind_code, kind in ((0, "U"), (1, "I")):
                     sel = kinds == kind_code
@@ -275,8 +279,10 @@ class ALSModelStore:
                                        device=self.device)
             self._rows.clear()
             self._mirror_len = 0
+            self._cand_version += 1
         row = self._rows.get(key)
         if row is None:
+            self._cand_version += 1
             if self._mirror_len == self._mirror.shape[0]:
                 bigger = torch.zeros(self._mirror.shape[0] * 2, k,
                                      dtype=torch.bfloat16, device=self.device)
@@ -314,6 +320,7 @@ class ALSModelStore:
                    else torch.arange(itf.shape[0]))
             self._blocks.add_block("U", uid, uf)
             self._blocks.add_block("I", iid, itf)
+            self._cand_version += 1
             if self._k is None:
                 self._k = int(user_factors.shape[1])
 
@@ -366,6 +373,7 @@ class ALSModelStore:
                 self._blocks.add_block(kind, ids[sel], facs[sel], text,
                                        offs[sel], lens[sel])
                 n += cnt
+            self._cand_version += 1
             if n:
                 # bulk rows supersede earlier scalar payloads (last-writer
                 # wins) — drop only the stale overlapping entries
@@ -468,6 +476,140 @@ class ALSModelStore:
                 si = (im if isrc == "m" else ia)[sel].to(V.device)
                 preds[sel] = ops.predict_dot(U, V, su, si).cpu()
         return preds, ok
+
+    # ---------------------------------------------------- recommendations
+
+    def _item_candidates(self) -> tuple:
+        """Live item rows per source, cached until a key gains a new row
+        (``_cand_version``): ``(version, (mirror_rows, mirror_ids),
+        (block_rows, block_ids))`` with rows as ascending int64 device
+        tensors (``None`` for an empty source) and ids as row -> item id.
+        Mirror: keys ending ``-I`` except MEAN-I (users and items share that
+        mirror).  Blocks: the "I" rows the idmap points at NOW (superseded
+        slots are not reachable from it) minus ids a mirror key shadows.
+        Caller holds ``_lock``."""
+        cache = self._cand_cache
+        if cache is not None and cache[0] == self._cand_version:
+            return cache
+        m_ids: Dict[int, str] = {
+            row: key[:-2] for key, row in self._rows.items()
+            if key.endswith("-I") and key != MEAN_ITEM_KEY}
+        b_ids: Dict[int, str] = {}
+        if self._blocks is not None:
+            b_ids = {row: str(eid)
+                     for eid, row in self._blocks.idmap["I"].items()
+                     if f"{eid}-I" not in self._rows}
+
+        def rows_of(ids: Dict[int, str]) -> Optional[torch.Tensor]:
+            if not ids:
+                return None
+            return torch.tensor(sorted(ids), dtype=torch.int64
+                                ).to(self.device)
+
+        cache = (self._cand_version, (rows_of(m_ids), m_ids),
+                 (rows_of(b_ids), b_ids))
+        self._cand_cache = cache
+        return cache
+
+    def recommend(self, user_ids: List[str], n: int,
+                  exclude: Optional[List[List[str]]] = None
+                  ) -> Tuple[List[bool], List[List[str]], List[List[float]]]:
+        """Top-``n`` items per user by ``dot(U[u], V[i])`` over every live
+        item of the store, through the fused score + top-k kernel: at most
+        one launch per item source (row-at-a-time mirror, attach/bulk
+        blocks), merged per user on the host.  Order: score descending,
+        then item id (numeric ids by value).  Which of several equal-score
+        items make the cut inside ONE source is decided by storage row
+        (earlier row first).  ``exclude[i]`` lists item ids user ``i`` must
+        not get (unknown ids are ignored).  Returns ``(found, items,
+        scores)``; an unknown user has ``found`` False and empty lists, and
+        a list is shorter than ``n`` when fewer items remain."""
+        from .. import ops
+        n = int(n)
+        if not 1 <= n <= 128:
+            raise ValueError(f"n must be in 1..128, got {n}")
+        if exclude is not None and len(exclude) != len(user_ids):
+            raise ValueError("exclude must hold one list per user")
+        with self._lock:
+            um, ua = self._batch_rows(user_ids, "U")
+            mirror = self._mirror
+            blocks = self._blocks
+            _, (m_cand, m_ids), (b_cand, b_ids) = self._item_candidates()
+            found_t = (um >= 0) | (ua >= 0)
+            sel = found_t.nonzero(as_tuple=True)[0].tolist()
+            # exclusion ids -> sorted rows per source (mirror shadows blocks)
+            ex_m: List[List[int]] = []
+            ex_b: List[List[int]] = []
+            if exclude is not None:
+                idmap = blocks.idmap["I"] if blocks is not None else {}
+                for qi in sel:
+                    rm, rb = set(), set()
+                    for item in exclude[qi]:
+                        row = self._rows.get(als_state_key(item, "I"))
+                        if row is not None:
+                            rm.add(row)
+                            continue
+                        try:
+                            row = idmap.get(int(item))
+                        except ValueError:
+                            row = None
+                        if row is not None:
+                            rb.add(row)
+                    ex_m.append(sorted(rm))
+                    ex_b.append(sorted(rb))
+        found = found_t.tolist()
+        items: List[List[str]] = [[] for _ in user_ids]
+        scores: List[List[float]] = [[] for _ in user_ids]
+        if not sel:
+            return found, items, scores
+        # query vectors gathered on the device, mirror first
+        k = (mirror if mirror is not None else blocks.dev["U"]).shape[1]
+        Q = torch.zeros(len(sel), k, dtype=torch.bfloat16, device=self.device)
+        sel_t = torch.tensor(sel, dtype=torch.int64)
+        in_m = um[sel_t] >= 0
+        if bool(in_m.any()):
+            Q[in_m.to(self.device)] = mirror[um[sel_t][in_m].to(self.device)]
+        if bool((~in_m).any()):
+            Q[(~in_m).to(self.device)] = blocks.dev["U"][
+                ua[sel_t][~in_m].to(self.device)]
+
+        def csr(lists: List[List[int]]):
+            if exclude is None:
+                return None
+            ptr = [0]
+            for rows in lists:
+                ptr.append(ptr[-1] + len(rows))
+            flat = [r for rows in lists for r in rows]
+            return (torch.tensor(ptr, dtype=torch.int64).to(self.device),
+                    torch.tensor(flat, dtype=torch.int64).to(self.device))
+
+        merged: List[List[Tuple[float, str]]] = [[] for _ in sel]
+        for V, cand, ids, ex in (
+                (mirror, m_cand, m_ids, ex_m),
+                (blocks.dev["I"] if blocks is not None and "I" in blocks.dev
+                 else None, b_cand, b_ids, ex_b)):
+            if V is None or cand is None:
+                continue
+            s, r = ops.topk_scores(Q, V, n, cand=cand, exclude=csr(ex))
+            s, r = s.cpu().tolist(), r.cpu().tolist()
+            for j in range(len(sel)):
+                merged[j].extend((sc, ids[row])
+                                 for sc, row in zip(s[j], r[j]) if row >= 0)
+
+        def order(entry: Tuple[float, str]):
+            sc, item = entry
+            try:
+                ident = (0, int(item), "")
+            except ValueError:
+                ident = (1, 0, item)
+            # NaN scores after every number, as in the kernel
+            return (1, 0.0, ident) if sc != sc else (0, -sc, ident)
+
+        for j, qi in enumerate(sel):
+            best = sorted(merged[j], key=order)[:n]
+            items[qi] = [item for _, item in best]
+            scores[qi] = [float(sc) for sc, _ in best]
+        return found, items, scores
 
     # -------------------------------------------------------- online SGD
 
