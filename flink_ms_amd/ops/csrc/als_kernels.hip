@@ -407,6 +407,13 @@ DEV_INLINE void wreg_trail(f32x4* T, const float* scr, const float* ndk,
 //                  per-lane product x0*id0 in the forward step)
 //   WREG_BC_HOIST  + branch-free substitution steps, the block's L entries
 //                  read ahead of the serial chain (the default)
+// Counters put the kernel at its VALU issue limit at WREG_BC_HOIST (VALU-
+// active cycles per SIMD ~ busy cycles, docs/KERNELS.md round 4), so that
+// level alone also sheds vector instructions that do not touch a bit:
+// packed pairs of panel updates (wreg_update2), keep-or-drop selects under
+// literal lane masks instead of per-step compares (wreg_select), and one
+// division per pivot shared by the substitutions and the trailing update.
+// Levels 0-2 stay the literal baseline the bit-identity tests compare to.
 #define WREG_BC_SHFL 0
 #define WREG_BC_PANEL 1
 #define WREG_BC_SUBST 2
@@ -443,6 +450,52 @@ DEV_INLINE float wreg_mul_sub(float acc, float a, float b) {
     return acc - a * b;
 }
 
+// Two neighbouring columns of one pivot step that round the same way
+// (wreg_update_unfused() agrees on both) as one packed operation: the
+// multiplier lscl is shared, only the broadcast differs.  Per element this
+// is exactly wreg_mul_sub() or __builtin_fmaf(-lscl, colj, seg); only the
+// instruction count changes (v_pk_mul + v_pk_add, or one v_pk_fma).
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+DEV_INLINE f32x2 wreg_update2(bool unfused, f32x2 acc, float lscl,
+                              f32x2 colj) {
+    const f32x2 l = {lscl, lscl};
+    if (unfused) {
+#pragma clang fp contract(off)
+        return acc - l * colj;
+    }
+    return __builtin_elementwise_fma(-l, colj, acc);
+}
+
+// columns (cc, cc+1), cc even, go packed when both round the same way; the
+// even alignment keeps one register pair per column pair over all pivots
+constexpr bool wreg_update_paired(int jj, int cc) {
+    return cc % 2 == 0 && cc > jj && cc + 1 < 16 &&
+           wreg_update_unfused(jj, cc) == wreg_update_unfused(jj, cc + 1);
+}
+
+// Keep-or-drop select under a lane set that is a compile-time constant:
+// the 64-bit mask is a literal in an SGPR pair, no per-step v_cmp.  Lanes
+// outside the mask keep `keep` untouched, whatever `take` holds.
+DEV_INLINE float wreg_select(unsigned long long mask, float take, float keep) {
+    // The mask's high word goes through an opaque 32-bit scalar move.  Left
+    // to the compiler, a mask whose high word is all ones (the k = 64 lane
+    // sets) becomes one s_mov_b64 with a 32-bit literal, meant sign-extended
+    // but encoded (and, on gfx950, executed) as the zero-extended low word:
+    // lanes 32..63 dropped out of the select and k = 64 came out wrong.
+    unsigned hi = (unsigned)(mask >> 32);
+    __asm__("" : "+s"(hi));
+    mask = ((unsigned long long)hi << 32) | (unsigned)mask;
+    float r;
+    __asm__("v_cndmask_b32 %0, %1, %2, %3"
+            : "=v"(r) : "v"(keep), "v"(take), "s"(mask));
+    return r;
+}
+
+constexpr unsigned long long wreg_lanes_below(int n) {   // lanes 0..n-1
+    return n >= 64 ? ~0ull : (1ull << n) - 1ull;
+}
+
 template <int KT, int PI, int BC>
 DEV_INLINE void wreg_panels(f32x4* T, float* scr, int lane, int g4, int li,
                             float& d0) {
@@ -465,6 +518,21 @@ DEV_INLINE void wreg_panels(f32x4* T, float* scr, int lane, int g4, int li,
                 const float lscl = seg[jj] * dinv;
 #pragma unroll
                 for (int cc = jj + 1; cc < 16; ++cc) {
+                    if constexpr (BC >= WREG_BC_HOIST) {
+                        if (cc % 2 == 1 && wreg_update_paired(jj, cc - 1))
+                            continue;          // done with its even partner
+                        if (wreg_update_paired(jj, cc)) {
+                            const f32x2 colj = {
+                                wreg_bcast<true>(seg[jj], cc),
+                                wreg_bcast<true>(seg[jj], cc + 1)};
+                            const f32x2 s = wreg_update2(
+                                wreg_update_unfused(jj, cc),
+                                f32x2{seg[cc], seg[cc + 1]}, lscl, colj);
+                            seg[cc] = s.x;
+                            seg[cc + 1] = s.y;
+                            continue;
+                        }
+                    }
                     const float colj = wreg_bcast<RL>(seg[jj], cc);
                     seg[cc] = wreg_update_unfused(jj, cc)
                                   ? wreg_mul_sub(seg[cc], lscl, colj)
@@ -475,21 +543,56 @@ DEV_INLINE void wreg_panels(f32x4* T, float* scr, int lane, int g4, int li,
             for (int cc = 0; cc < 16; ++cc) scr[lane * 17 + cc] = seg[cc];
         }
         WREG_FENCE();
-        if (lane >= P0 && lane < P0 + 16)
-            d0 = scr[(lane - P0) * 17 + (lane - P0)];
-        wreg_load_col<KT, PI, PI>(T, scr, g4, li);
-        if constexpr (PI + 1 < KT) {
-            float ndk[4];
+        if constexpr (BC >= WREG_BC_HOIST) {
+            // The panel's 16 pivots are final: ONE guarded division per
+            // pivot serves the substitutions' 1/d (d0 carries the
+            // reciprocal itself at this level, see wreg_id0) and, through
+            // the scratch's unused pad column (word 16 of the stride-17
+            // rows), the trailing update's -1/d.  IEEE division is
+            // correctly rounded and rounding is symmetric in sign, so
+            // -(1.0f / d) == -1.0f / d bit for bit; the negation is a
+            // source modifier of the multiply that consumes it.  Every
+            // lane divides (the four lanes of an li write the same word).
+            const float d = scr[li * 17 + li];
+            const float rinv = d > 0.0f ? 1.0f / d : 0.0f;
+            scr[li * 17 + 16] = rinv;
+            d0 = wreg_select(0xffffull << P0, rinv, d0);
+            wreg_load_col<KT, PI, PI>(T, scr, g4, li);
+            if constexpr (PI + 1 < KT) {
+                WREG_FENCE();
+                float ndk[4];
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const int c = 4 * kk + g4;
-                const float d = scr[c * 17 + c];
-                ndk[kk] = d > 0.0f ? -1.0f / d : 0.0f;
+                for (int kk = 0; kk < 4; ++kk)
+                    ndk[kk] = -scr[(4 * kk + g4) * 17 + 16];
+                wreg_trail<KT, PI, PI + 1, PI + 1>(T, scr, ndk, g4, li);
             }
-            wreg_trail<KT, PI, PI + 1, PI + 1>(T, scr, ndk, g4, li);
+        } else {
+            if (lane >= P0 && lane < P0 + 16)
+                d0 = scr[(lane - P0) * 17 + (lane - P0)];
+            wreg_load_col<KT, PI, PI>(T, scr, g4, li);
+            if constexpr (PI + 1 < KT) {
+                float ndk[4];
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) {
+                    const int c = 4 * kk + g4;
+                    const float d = scr[c * 17 + c];
+                    ndk[kk] = d > 0.0f ? -1.0f / d : 0.0f;
+                }
+                wreg_trail<KT, PI, PI + 1, PI + 1>(T, scr, ndk, g4, li);
+            }
         }
         wreg_panels<KT, PI + 1, BC>(T, scr, lane, g4, li, d0);
     }
+}
+
+// The substitutions' 1/d from what wreg_panels left in d0: the row's pivot
+// (divided here) below WREG_BC_HOIST, the panel's shared reciprocal above.
+template <int BC>
+DEV_INLINE float wreg_id0(float d0) {
+    if constexpr (BC >= WREG_BC_HOIST)
+        return d0;
+    else
+        return d0 > 0.0f ? 1.0f / d0 : 0.0f;
 }
 
 template <int KT, int J, int BC>
@@ -522,7 +625,10 @@ DEV_INLINE void wreg_forward(const f32x4* T, float* scr, float& x0,
                         const int j = B0 + t0 + u;
                         const float zj = wreg_bcast<true>(x0 * id0, j);
                         const float xn = __builtin_fmaf(-l[u], zj, x0);
-                        x0 = (lane > j && lane < K) ? xn : x0;
+                        // lanes j+1 .. K-1
+                        x0 = wreg_select(wreg_lanes_below(K) &
+                                             ~wreg_lanes_below(j + 1),
+                                         xn, x0);
                     }
                 }
             }
@@ -580,7 +686,7 @@ DEV_INLINE void wreg_backward(const f32x4* T, float* scr, float& x0,
                         const int c = B0 + t1 - 1 - u;
                         const float xc = wreg_bcast<true>(x0, c);
                         const float xn = __builtin_fmaf(-m[u], xc, x0);
-                        x0 = (lane < c) ? xn : x0;
+                        x0 = wreg_select(wreg_lanes_below(c), xn, x0);
                     }
                 }
             }
@@ -599,6 +705,20 @@ DEV_INLINE void wreg_backward(const f32x4* T, float* scr, float& x0,
     }
 }
 
+// What the register-LDL kernels store for a NaN result: the canonical quiet
+// NaN.  Sign and payload of a NaN say nothing about the system, and they
+// are not the source's to decide: they follow where the compiler puts a
+// negation (on a multiply's operand, on an FMA's, or into the reciprocal's
+// select) and in which order it hands two NaN operands to an instruction,
+// and it chooses differently at each broadcast level.  On integer bits, so
+// that no floating-point fold can see through it.
+DEV_INLINE float wreg_canon_nan(float x) {
+    const unsigned u = __builtin_bit_cast(unsigned, x);
+    return __builtin_bit_cast(float,
+                              (u & 0x7fffffffu) > 0x7f800000u ? 0x7fc00000u
+                                                              : u);
+}
+
 template <int KT, int t>
 DEV_INLINE void wreg_load_A(f32x4* T, const float* src, int g4, int li) {
     if constexpr (t < KT * (KT + 1) / 2) {
@@ -614,6 +734,9 @@ DEV_INLINE void wreg_load_A(f32x4* T, const float* src, int g4, int li) {
 
 template <int KT, int BC>
 __launch_bounds__(256)
+// the lean variant sits at 75 VGPRs; left alone the allocator adds 24 AGPRs
+// on top and lands one register granule past 5 waves per SIMD
+__attribute__((amdgpu_waves_per_eu(BC >= WREG_BC_HOIST ? 5 : 1)))
 __global__ void k_ldl_solve_wave_reg(const float* __restrict__ A_in,
                                      const float* __restrict__ b_in,
                                      float* __restrict__ x_out,
@@ -637,10 +760,11 @@ __global__ void k_ldl_solve_wave_reg(const float* __restrict__ A_in,
     float x0 = (lane < K) ? b_in[e * K + lane] : 0.0f;
     float d0 = 1.0f;
     wreg_panels<KT, 0, BC>(T, scr, lane, g4, li, d0);
-    const float id0 = d0 > 0.0f ? 1.0f / d0 : 0.0f;
+    const float id0 = wreg_id0<BC>(d0);
     wreg_forward<KT, 0, BC>(T, scr, x0, id0, lane, g4, li);
     x0 *= id0;
     wreg_backward<KT, KT - 1, BC>(T, scr, x0, id0, lane, g4, li);
+    x0 = wreg_canon_nan(x0);
     if (lane < K) {
         x_out[e * K + lane] = x0;
         if (x_bf16) x_bf16[e * K + lane] = f2bf(x0);
@@ -706,17 +830,43 @@ DEV_INLINE void wavefused_dump_b(const f32x4* E, float* scr, int g4, int li) {
     }
 }
 
-template <int KT, int I = 0>
-DEV_INLINE void wavefused_diag(f32x4* T, float regn, int g4, int li) {
+// Rounding of diag + reg*n, pinned like the panel updates above.  Written
+// as T + regn the contraction is the compiler's choice, and it chose by
+// basic block: every instantiation of the branching form below fuses the
+// product into the add (one rounding) except, at k = 64, for the diagonal
+// tiles past the first, whose adds sink behind the first panel and take
+// the rounded product (read off the ISA of every instantiation).  The
+// branch-free form would be fused everywhere, so it spells the split out.
+constexpr bool wavefused_diag_unfused(int KT, int I) {
+    return KT == 4 && I >= 1;
+}
+
+DEV_INLINE float wreg_mul_add(float acc, float a, float b) {
+#pragma clang fp contract(off)
+    return acc + a * b;
+}
+
+template <int KT, int BC, int I = 0>
+DEV_INLINE void wavefused_diag(f32x4* T, float reg, float nf, int g4,
+                               int li) {
     if constexpr (I < KT) {
         constexpr int t = tri_off(I, I);
+        const float regn = reg * nf;
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (li == g4 * 4 + r) {
+        for (int r = 0; r < 4; ++r) {
+            if constexpr (BC >= WREG_BC_HOIST) {
+                // li == g4*4 + r holds on lanes 20*g4 + r: a constant set
+                const float dd = wavefused_diag_unfused(KT, I)
+                                     ? wreg_mul_add(T[t][r], reg, nf)
+                                     : __builtin_fmaf(reg, nf, T[t][r]);
+                T[t][r] = wreg_select(0x1000010000100001ull << r,
+                                      dd <= 0.0f ? 1.0f : dd, T[t][r]);
+            } else if (li == g4 * 4 + r) {
                 const float dd = T[t][r] + regn;
                 T[t][r] = dd <= 0.0f ? 1.0f : dd;   // degenerate guard
             }
-        wavefused_diag<KT, I + 1>(T, regn, g4, li);
+        }
+        wavefused_diag<KT, BC, I + 1>(T, reg, nf, g4, li);
     }
 }
 
@@ -869,13 +1019,14 @@ __global__ void k_als_solve_wavefused_db(const long long* __restrict__ indptr,
     WREG_FENCE();
     float x0 = (lane < K) ? scr[lane] + scr[64 + lane] : 0.0f;
     WREG_FENCE();
-    wavefused_diag<KT>(T, reg * (float)n, g4, li);
+    wavefused_diag<KT, BC>(T, reg, (float)n, g4, li);
     float d0 = 1.0f;
     wreg_panels<KT, 0, BC>(T, scr, lane, g4, li, d0);
-    const float id0 = d0 > 0.0f ? 1.0f / d0 : 0.0f;
+    const float id0 = wreg_id0<BC>(d0);
     wreg_forward<KT, 0, BC>(T, scr, x0, id0, lane, g4, li);
     x0 *= id0;
     wreg_backward<KT, KT - 1, BC>(T, scr, x0, id0, lane, g4, li);
+    x0 = wreg_canon_nan(x0);
     if (lane < K) {
         out_f32[e * K + lane] = x0;
         if (out_bf16) out_bf16[e * K + lane] = f2bf(x0);
@@ -985,14 +1136,15 @@ __global__ void k_als_solve_wavefused(const long long* __restrict__ indptr,
     WREG_FENCE();
     float x0 = (lane < K) ? scr[lane] + scr[64 + lane] : 0.0f;
     WREG_FENCE();                      // b read before panel dumps reuse scr
-    wavefused_diag<KT>(T, reg * (float)n, g4, li);
+    wavefused_diag<KT, BC>(T, reg, (float)n, g4, li);
     // in-register LDL + substitution (shared with k_ldl_solve_wave_reg)
     float d0 = 1.0f;
     wreg_panels<KT, 0, BC>(T, scr, lane, g4, li, d0);
-    const float id0 = d0 > 0.0f ? 1.0f / d0 : 0.0f;
+    const float id0 = wreg_id0<BC>(d0);
     wreg_forward<KT, 0, BC>(T, scr, x0, id0, lane, g4, li);
     x0 *= id0;
     wreg_backward<KT, KT - 1, BC>(T, scr, x0, id0, lane, g4, li);
+    x0 = wreg_canon_nan(x0);
     if (lane < K) {
         out_f32[e * K + lane] = x0;
         if (out_bf16) out_bf16[e * K + lane] = f2bf(x0);
