@@ -43,9 +43,8 @@
 //          k_gramian, which only exports A, keeps the square [K][K+1]
 //          image (write_acc mirrors the upper tiles into it).
 //
-// File layout: kernels first (block path, wave solvers, wave-fused,
-// wave-quad, MFMA probes), then every extern "C" launcher declared in
-// fma_api.h.
+// File layout: kernels first (block path, wave solvers, wave-fused, MFMA
+// probes), then every extern "C" launcher declared in fma_api.h.
 
 #include "common.hip.h"
 
@@ -1152,395 +1151,6 @@ __global__ void k_als_solve_wavefused(const long long* __restrict__ indptr,
     }
 }
 
-// ------- wave-QUAD fused ALS solve (64 < k <= 128, fp8 gathers) -------
-// The k=128 block-fused kernel serializes its LDL at Gramian occupancy and
-// the modular path pays an 80 GB A round trip; this kernel extends the
-// k<=64 wave-fused design: all FOUR waves of a block own ONE entity, each
-// holding a quarter of the lower-triangle MFMA C-fragment tiles (t % 4 ==
-// wave).  The Gramian accumulates straight into those registers (4 staged
-// chunks in flight per entity), then an in-register LDL runs with block
-// barriers at phase edges: panel columns bounce through LDS scratch,
-// 16-col panels factor on wave 0 (2 rows/lane), trailing updates run on
-// every wave's own tiles via f32 MFMA, and the substitutions keep x as
-// TWO registers per lane (rows lane and lane+64) redundantly on each wave
-// so the serial chain needs no cross-wave traffic.  One entity per block
-// keeps every barrier trivially uniform (n==0 exits whole-block).
-
-template <int KT, int P, int t = 0>
-DEV_INLINE void wq_mfma(const fp8x8* frag, f32x4* T, f32x4* E) {
-    constexpr int NA = KT * (KT + 1) / 2;
-    if constexpr (t < NA) {
-        if constexpr ((t & 3) == P) {
-            constexpr int I = lo_tile_i(t);
-            constexpr int J = t - (I * (I + 1)) / 2;
-            T[t >> 2] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(
-                frag[I], frag[J], T[t >> 2], 0, 0, 0);
-        }
-        wq_mfma<KT, P, t + 1>(frag, T, E);
-    } else if constexpr (t < NA + KT) {
-        constexpr int Pt = t - NA;
-        if constexpr ((Pt & 3) == P)
-            E[Pt >> 2] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(
-                frag[Pt], frag[KT], E[Pt >> 2], 0, 0, 0);
-        wq_mfma<KT, P, t + 1>(frag, T, E);
-    }
-}
-
-template <int KT, int P, int Pt = 0>
-DEV_INLINE void wq_dump_b(const f32x4* E, float* scr, int g4, int li) {
-    constexpr int K = KT * 16;
-    if constexpr (Pt < KT) {
-        if constexpr ((Pt & 3) == P) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (li == 0) scr[Pt * 16 + g4 * 4 + r] = E[Pt >> 2][r];
-                else if (li == 1)
-                    scr[K + Pt * 16 + g4 * 4 + r] = E[Pt >> 2][r];
-            }
-        }
-        wq_dump_b<KT, P, Pt + 1>(E, scr, g4, li);
-    }
-}
-
-template <int KT, int P, int I = 0>
-DEV_INLINE void wq_diag(f32x4* T, float regn, int g4, int li) {
-    if constexpr (I < KT) {
-        constexpr int t = tri_off(I, I);
-        if constexpr ((t & 3) == P) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (li == g4 * 4 + r) {
-                    const float dd = T[t >> 2][r] + regn;
-                    T[t >> 2][r] = dd <= 0.0f ? 1.0f : dd;
-                }
-        }
-        wq_diag<KT, P, I + 1>(T, regn, g4, li);
-    }
-}
-
-// dump / load the PI-th 16-column panel (tiles (I,PI), I>=PI) to/from scr
-// rows relative to P0, stride 17 — each wave handles its owned tiles
-template <int KT, int PI, int P, int I = PI>
-DEV_INLINE void wq_dump_col(const f32x4* T, float* scr, int g4, int li) {
-    if constexpr (I < KT) {
-        constexpr int t = tri_off(I, PI);
-        if constexpr ((t & 3) == P) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                scr[((I - PI) * 16 + g4 * 4 + r) * 17 + li] = T[t >> 2][r];
-        }
-        wq_dump_col<KT, PI, P, I + 1>(T, scr, g4, li);
-    }
-}
-
-template <int KT, int PI, int P, int I = PI>
-DEV_INLINE void wq_load_col(f32x4* T, const float* scr, int g4, int li) {
-    if constexpr (I < KT) {
-        constexpr int t = tri_off(I, PI);
-        if constexpr ((t & 3) == P) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                T[t >> 2][r] = scr[((I - PI) * 16 + g4 * 4 + r) * 17 + li];
-        }
-        wq_load_col<KT, PI, P, I + 1>(T, scr, g4, li);
-    }
-}
-
-template <int KT, int PI, int P, int RB, int CB>
-DEV_INLINE void wq_trail(f32x4* T, const float* scr, const float* ndk,
-                         int g4, int li) {
-    if constexpr (RB < KT) {
-        if constexpr (CB > RB) {
-            wq_trail<KT, PI, P, RB + 1, PI + 1>(T, scr, ndk, g4, li);
-        } else {
-            constexpr int t = tri_off(RB, CB);
-            if constexpr ((t & 3) == P) {
-                f32x4 acc = T[t >> 2];
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    const int pc = 4 * kk + g4;
-                    const float a = scr[((RB - PI) * 16 + li) * 17 + pc];
-                    const float b =
-                        scr[((CB - PI) * 16 + li) * 17 + pc] * ndk[kk];
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc,
-                                                               0, 0, 0);
-                }
-                T[t >> 2] = acc;
-            }
-            wq_trail<KT, PI, P, RB, CB + 1>(T, scr, ndk, g4, li);
-        }
-    }
-}
-
-// LDL panel loop: dump column -> factor (wave 0, 2 rows/lane) -> load the
-// factored column back -> trailing MFMA on owned tiles.  Uniform barriers.
-template <int KT, int P, int PI = 0>
-DEV_INLINE void wq_panels(f32x4* T, float* scr, int lane, int g4, int li,
-                          int w, float& da, float& db) {
-    if constexpr (PI < KT) {
-        constexpr int K = KT * 16;
-        constexpr int P0 = 16 * PI;
-        constexpr int NR = K - P0;          // rows in this panel image
-        wq_dump_col<KT, PI, P>(T, scr, g4, li);
-        __syncthreads();
-        if (w == 0) {   // factor: lane owns panel rows rel lane, lane+64
-            float sa[16], sb[16];
-            const bool av = lane < NR, bv = lane + 64 < NR;
-            if (av) {
-#pragma unroll
-                for (int cc = 0; cc < 16; ++cc) sa[cc] = scr[lane * 17 + cc];
-            }
-            if (bv) {
-#pragma unroll
-                for (int cc = 0; cc < 16; ++cc)
-                    sb[cc] = scr[(lane + 64) * 17 + cc];
-            }
-#pragma unroll
-            for (int jj = 0; jj < 15; ++jj) {
-                const float dj = __shfl(sa[jj], jj, WAVE);
-                const float dinv = dj > 0.0f ? 1.0f / dj : 0.0f;
-                const float la = sa[jj] * dinv, lb = sb[jj] * dinv;
-#pragma unroll
-                for (int cc = jj + 1; cc < 16; ++cc) {
-                    const float colj = __shfl(sa[jj], cc, WAVE);
-                    sa[cc] -= la * colj;
-                    sb[cc] -= lb * colj;
-                }
-            }
-            if (av) {
-#pragma unroll
-                for (int cc = 0; cc < 16; ++cc) scr[lane * 17 + cc] = sa[cc];
-            }
-            if (bv) {
-#pragma unroll
-                for (int cc = 0; cc < 16; ++cc)
-                    scr[(lane + 64) * 17 + cc] = sb[cc];
-            }
-        }
-        __syncthreads();
-        // raw diagonal of this panel's rows -> per-lane d registers
-        if ((lane >> 4) == PI)
-            da = scr[(lane - P0) * 17 + (lane - P0)];
-        if constexpr (P0 >= 64) {
-            if ((lane >> 4) + 4 == PI)
-                db = scr[(lane + 64 - P0) * 17 + (lane + 64 - P0)];
-        }
-        // load the FACTORED panel column back into the register tiles (the
-        // substitutions dump L from T; without this they would read raw A)
-        wq_load_col<KT, PI, P>(T, scr, g4, li);
-        if constexpr (PI + 1 < KT) {
-            float ndk[4];
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const float d = scr[(4 * kk + g4) * 17 + (4 * kk + g4)];
-                ndk[kk] = d > 0.0f ? -1.0f / d : 0.0f;
-            }
-            wq_trail<KT, PI, P, PI + 1, PI + 1>(T, scr, ndk, g4, li);
-        }
-        __syncthreads();   // trailing reads done before next panel's dump
-        wq_panels<KT, P, PI + 1>(T, scr, lane, g4, li, w, da, db);
-    }
-}
-
-// forward substitution: x as 2 regs/lane (rows lane, 64+lane), redundant
-// on every wave; column-J tiles bounce through scr per block of 16
-template <int KT, int P, int J = 0>
-DEV_INLINE void wq_forward(const f32x4* T, float* scr, float& xa, float& xb,
-                           float ida, float idb, int lane, int g4, int li) {
-    if constexpr (J < KT) {
-        constexpr int K = KT * 16;
-        constexpr int B0 = 16 * J;
-        wq_dump_col<KT, J, P>(T, scr, g4, li);
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const int j = B0 + t;
-            if (j >= K - 1) break;
-            float zj;
-            if constexpr (B0 < 64) {
-                zj = __shfl(xa, j, WAVE) * __shfl(ida, j, WAVE);
-            } else {
-                zj = __shfl(xb, j - 64, WAVE) * __shfl(idb, j - 64, WAVE);
-            }
-            if (lane > j) xa -= scr[(lane - B0) * 17 + t] * zj;
-            if (64 + lane > j && 64 + lane < K)
-                xb -= scr[(64 + lane - B0) * 17 + t] * zj;
-        }
-        __syncthreads();
-        wq_forward<KT, P, J + 1>(T, scr, xa, xb, ida, idb, lane, g4, li);
-    }
-}
-
-// backward: row image of tile-row I (16 rows x K cols, stride K+1)
-template <int KT, int I, int P, int J = 0>
-DEV_INLINE void wq_dump_row(const f32x4* T, float* scr, int g4, int li) {
-    if constexpr (J <= I) {
-        constexpr int K = KT * 16;
-        constexpr int t = tri_off(I, J);
-        if constexpr ((t & 3) == P) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                scr[(g4 * 4 + r) * (K + 1) + J * 16 + li] = T[t >> 2][r];
-        }
-        wq_dump_row<KT, I, P, J + 1>(T, scr, g4, li);
-    }
-}
-
-template <int KT, int P, int I = KT - 1>
-DEV_INLINE void wq_backward(const f32x4* T, float* scr, float& xa, float& xb,
-                            float ida, float idb, int lane, int g4, int li) {
-    if constexpr (I >= 0) {
-        constexpr int K = KT * 16;
-        constexpr int B0 = 16 * I;
-        wq_dump_row<KT, I, P>(T, scr, g4, li);
-        __syncthreads();
-#pragma unroll
-        for (int t = 15; t >= 0; --t) {
-            const int c = B0 + t;
-            if (c < 1) break;
-            float xc;
-            if constexpr (B0 >= 64) {
-                xc = __shfl(xb, c - 64, WAVE);
-            } else {
-                xc = __shfl(xa, c, WAVE);
-            }
-            if (lane < c) xa -= scr[t * (K + 1) + lane] * ida * xc;
-            if (64 + lane < c && 64 + lane < K)
-                xb -= scr[t * (K + 1) + 64 + lane] * idb * xc;
-        }
-        __syncthreads();
-        wq_backward<KT, P, I - 1>(T, scr, xa, xb, ida, idb, lane, g4, li);
-    }
-}
-
-template <int KT>
-__launch_bounds__(256)
-__global__ void k_als_solve_wavefused2(const long long* __restrict__ indptr,
-                                       const int* __restrict__ indices,
-                                       const float* __restrict__ values,
-                                       const unsigned char* __restrict__ factors,
-                                       float* __restrict__ out_f32,
-                                       unsigned char* __restrict__ out_fp8,
-                                       const int* __restrict__ row_order,
-                                       long long nrows, float reg) {
-    constexpr int K = KT * 16;
-    static_assert(K > 64 && K <= 128, "wave-quad path: 64 < k <= 128");
-    constexpr int NA = KT * (KT + 1) / 2;
-    constexpr int NOWN = (NA + 3) / 4;
-    constexpr int NE = (KT + 3) / 4;
-    constexpr int TROW = Geo<KT>::TROW8;
-    constexpr int SB = (K + 16) * TROW;
-    constexpr int SCRF = (K * 17 > 16 * (K + 1)) ? K * 17 : 16 * (K + 1);
-    constexpr int BB0 = (4 * SB > SCRF * 4) ? 4 * SB : SCRF * 4;
-    constexpr int BB = (BB0 + 15) & ~15;
-    __shared__ __align__(16) char smem[BB];
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int g4 = lane >> 4, li = lane & 15;
-    float* scr = (float*)smem;
-    long long e = blockIdx.x;
-    if (e >= nrows) return;
-    if (row_order) e = row_order[e];
-    const long long p0 = indptr[e];
-    const int n = (int)(indptr[e + 1] - p0);
-    if (n == 0) {   // block-uniform: every wave exits together
-        for (int c = threadIdx.x; c < K; c += 256) {
-            out_f32[e * K + c] = 0.0f;
-            if (out_fp8) out_fp8[e * K + c] = 0;
-        }
-        return;
-    }
-    {   // zero EXT pad rows of my stage buffer
-        char* buf = smem + (long long)w * SB;
-        for (int i = lane; i < 14 * 8; i += WAVE) {
-            const int row = K + 2 + i / 8, seg = i % 8;
-            *(unsigned*)(buf + (long long)row * TROW + seg * 4) = 0u;
-        }
-    }
-    f32x4 T[NOWN], E[NE];
-#pragma unroll
-    for (int t = 0; t < NOWN; ++t) T[t] = f32x4{0, 0, 0, 0};
-#pragma unroll
-    for (int t = 0; t < NE; ++t) E[t] = f32x4{0, 0, 0, 0};
-    const int nch = (n + 31) >> 5;
-    for (int r0 = 0; r0 < nch; r0 += 4) {
-        if (r0 + w < nch)
-            stage_chunk_w<KT, true>(smem + (long long)w * SB, indices,
-                                    values, factors,
-                                    p0 + (long long)(r0 + w) * 32,
-                                    n - (r0 + w) * 32, lane);
-        __syncthreads();
-        const int ns = min(4, nch - r0);
-#pragma unroll 1
-        for (int sc = 0; sc < ns; ++sc) {
-            fp8x8 frag[KT + 1];
-            read_frags<KT, true>(smem + (long long)sc * SB, lane, frag);
-            switch (w) {
-                case 0: wq_mfma<KT, 0>(frag, T, E); break;
-                case 1: wq_mfma<KT, 1>(frag, T, E); break;
-                case 2: wq_mfma<KT, 2>(frag, T, E); break;
-                default: wq_mfma<KT, 3>(frag, T, E); break;
-            }
-        }
-        __syncthreads();
-    }
-    // b = hi + lo via scr rows [0,K) hi, [K,2K) lo
-    switch (w) {
-        case 0: wq_dump_b<KT, 0>(E, scr, g4, li); break;
-        case 1: wq_dump_b<KT, 1>(E, scr, g4, li); break;
-        case 2: wq_dump_b<KT, 2>(E, scr, g4, li); break;
-        default: wq_dump_b<KT, 3>(E, scr, g4, li); break;
-    }
-    __syncthreads();
-    float xa = scr[lane] + scr[K + lane];
-    float xb = (64 + lane < K) ? scr[64 + lane] + scr[K + 64 + lane] : 0.0f;
-    __syncthreads();   // b read before the panel dumps reuse scr
-    float da = 1.0f, db = 1.0f;
-    const float regn = reg * (float)n;
-    switch (w) {
-        case 0:
-            wq_diag<KT, 0>(T, regn, g4, li);
-            wq_panels<KT, 0>(T, scr, lane, g4, li, w, da, db);
-            break;
-        case 1:
-            wq_diag<KT, 1>(T, regn, g4, li);
-            wq_panels<KT, 1>(T, scr, lane, g4, li, w, da, db);
-            break;
-        case 2:
-            wq_diag<KT, 2>(T, regn, g4, li);
-            wq_panels<KT, 2>(T, scr, lane, g4, li, w, da, db);
-            break;
-        default:
-            wq_diag<KT, 3>(T, regn, g4, li);
-            wq_panels<KT, 3>(T, scr, lane, g4, li, w, da, db);
-            break;
-    }
-    const float ida = da > 0.0f ? 1.0f / da : 0.0f;
-    const float idb = db > 0.0f ? 1.0f / db : 0.0f;
-    switch (w) {
-        case 0: wq_forward<KT, 0>(T, scr, xa, xb, ida, idb, lane, g4, li); break;
-        case 1: wq_forward<KT, 1>(T, scr, xa, xb, ida, idb, lane, g4, li); break;
-        case 2: wq_forward<KT, 2>(T, scr, xa, xb, ida, idb, lane, g4, li); break;
-        default: wq_forward<KT, 3>(T, scr, xa, xb, ida, idb, lane, g4, li); break;
-    }
-    xa *= ida;
-    xb *= idb;
-    switch (w) {
-        case 0: wq_backward<KT, 0>(T, scr, xa, xb, ida, idb, lane, g4, li); break;
-        case 1: wq_backward<KT, 1>(T, scr, xa, xb, ida, idb, lane, g4, li); break;
-        case 2: wq_backward<KT, 2>(T, scr, xa, xb, ida, idb, lane, g4, li); break;
-        default: wq_backward<KT, 3>(T, scr, xa, xb, ida, idb, lane, g4, li); break;
-    }
-    if (w == 0) {
-        out_f32[e * K + lane] = xa;
-        if (out_fp8) out_fp8[e * K + lane] = f2fp8(xa);
-        if (64 + lane < K) {
-            out_f32[e * K + 64 + lane] = xb;
-            if (out_fp8) out_fp8[e * K + 64 + lane] = f2fp8(xb);
-        }
-    }
-}
-
 // ------------------------------------------------------------- MFMA probes
 // Layout-validation kernels for tests/test_gpu_mfma.py.
 
@@ -1782,20 +1392,6 @@ extern "C" int fma_als_solve_wavefused(
                         out_fp8, row_order, nrows, reg);
             return hipGetLastError();
         });
-    });
-}
-
-extern "C" int fma_als_solve_wavefused2(
-    int k, const long long* indptr, const int* indices, const float* values,
-    const unsigned char* factors, float* out_f32, unsigned char* out_fp8,
-    const int* row_order, long long nrows, float reg, void* stream) {
-    if (bad_shape(k, nrows)) return hipErrorInvalidValue;
-    return dispatch_ic<5, 6, 7, 8>(k / 16, [&](auto kt) {
-        k_als_solve_wavefused2<decltype(kt)::value>
-            <<<grid_block(nrows), kBlock, 0, (hipStream_t)stream>>>(
-                indptr, indices, values, factors, out_f32, out_fp8,
-                row_order, nrows, reg);
-        return hipGetLastError();
     });
 }
 

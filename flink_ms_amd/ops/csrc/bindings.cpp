@@ -380,27 +380,6 @@ void als_solve_wavefused_db(torch::Tensor indptr, torch::Tensor indices,
               a.name());
 }
 
-// wave-quad fused path for 64 < k <= 128 (e4m3 gathers only)
-void als_solve_wavefused2(torch::Tensor indptr, torch::Tensor indices,
-                          torch::Tensor values, torch::Tensor factors,
-                          torch::Tensor out_f32, torch::Tensor out_fp8,
-                          torch::Tensor row_order, double reg,
-                          int64_t stream) {
-    Args a("als_solve_wavefused2");
-    const int64_t nrows = a.csr(indptr, indices, values);
-    const int k = a.factors(factors, /*fp8=*/true, "factors");
-    a.rows(out_f32, kF32, "out_f32", nrows, k);
-    unsigned char* o8 =
-        a.optional(out_fp8, kU8, "out_fp8", out_f32.numel()) ? u8(out_fp8)
-                                                             : nullptr;
-    const int* order = a.row_order(row_order, nrows);
-    check_hip(fma_als_solve_wavefused2(
-                  k, i64(indptr), i32(indices), f32(values), u8(factors),
-                  f32(out_f32), o8, order, nrows, (float)reg,
-                  a.stream(stream)),
-              a.name());
-}
-
 // Batched solves A x = b from dense systems: A [n][k][k], b and x
 // [>= n][k].  Returns (n, k) through the out-parameters.
 void solve_args(Args& a, const torch::Tensor& A, const torch::Tensor& b,
@@ -721,7 +700,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("factors"), py::arg("out_f32"), py::arg("out_bf16"),
           py::arg("out_fp8"), py::arg("row_order"), py::arg("reg"),
           py::arg("stream"), py::arg("variant") = kBroadcastDefault);
-    m.def("als_solve_wavefused2", &als_solve_wavefused2);
     m.def("cholesky_solve", &cholesky_solve);
     m.def("cholesky_solve_ph", &cholesky_solve_ph);
     m.def("ldl_solve_wave", &ldl_solve_wave);

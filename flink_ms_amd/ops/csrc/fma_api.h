@@ -61,12 +61,6 @@ int fma_als_solve_wavefused_db(int k, const long long* indptr,
                                unsigned char* out_fp8, const int* row_order,
                                long long nrows, float reg, int variant,
                                void* stream);
-// ---- ALS, wave-quad path (k = 80..128, e4m3 factors only)
-int fma_als_solve_wavefused2(int k, const long long* indptr,
-                             const int* indices, const float* values,
-                             const unsigned char* factors, float* out_f32,
-                             unsigned char* out_fp8, const int* row_order,
-                             long long nrows, float reg, void* stream);
 
 // ---- MFMA layout probes: fixed-size operands (als_kernels.hip)
 int fma_mfma_probe_f32(const float* A /*[16][4]*/, const float* B /*[4][16]*/,

@@ -157,9 +157,7 @@ def test_als_trainer_gpu_converges(gpu):
     assert res.mse < 0.1 * var, f"GPU ALS MSE {res.mse} vs rating var {var}"
 
 
-@pytest.mark.parametrize("k", [16, 32, 64])
-def test_ldl_wave_solver_parity(gpu, k):
-    import flink_ms_amd._hip_ops as hip
+def _check_ldl_solver_parity(solve, gpu, k):
     g = torch.Generator().manual_seed(21)
     B = 257  # odd batch exercises the tail wave
     M = torch.randn(B, k, k, generator=g) * 0.3
@@ -169,13 +167,27 @@ def test_ldl_wave_solver_parity(gpu, k):
     xb = torch.empty(B, k, dtype=torch.bfloat16, device=gpu)
     x8 = torch.empty(B, k, dtype=torch.uint8, device=gpu)
     st = torch.cuda.current_stream().cuda_stream
-    hip.ldl_solve_wave(A, b, x, xb, x8, st)
+    solve(A, b, x, xb, x8, st)
     x_ref = R.cholesky_solve_reference(A.cpu(), b.cpu()).to(gpu)
     torch.cuda.synchronize()
     assert torch.allclose(x, x_ref, atol=1e-3, rtol=1e-3)
     assert torch.allclose(xb.to(torch.float32), x, atol=1e-1, rtol=2e-2)
     # the e4m3 image must be the RNE quantization of the fp32 solution
     assert torch.equal(x8.cpu(), ops.quantize_fp8(x.cpu()))
+
+
+@pytest.mark.parametrize("k", [16, 32, 64])
+def test_ldl_wave_solver_parity(gpu, k):
+    import flink_ms_amd._hip_ops as hip
+    _check_ldl_solver_parity(hip.ldl_solve_wave, gpu, k)
+
+
+@pytest.mark.parametrize("k", [16, 32, 48, 64])
+def test_ldl_wave_reg_solver_parity(gpu, k):
+    """The register wave solver (default broadcast variant) on the same SPD
+    systems, with the same assertions."""
+    import flink_ms_amd._hip_ops as hip
+    _check_ldl_solver_parity(hip.ldl_solve_wave_reg, gpu, k)
 
 
 def test_slabbed_solve_matches_unslabbed(gpu):
@@ -388,25 +400,18 @@ def test_wavefused_matches_modular(gpu, dtype, k):
 
 
 @pytest.mark.parametrize("k", [80, 96, 128])
-def test_wavefused2_matches_block_fused(gpu, k):
-    """The wave-pair register LDL (64<k<=128) and the block-fused kernel
-    must BOTH match the fp32 reference on the same quantized inputs
-    (comparing against ground truth pinpoints which kernel is wrong when
-    they disagree), plus odd tails and empty rows."""
+def test_block_fused_fp8_mid_ranks(gpu, k):
+    """The block-fused kernel with e4m3 gathers at 64 < k <= 128 (k = 80 and
+    96 have no other test) must match the fp32 reference on the same
+    quantized inputs and write the e4m3 image of its own solution, plus odd
+    tails and empty rows."""
     csr = _rand_csr(rows=401, cols=250, nnz=40_000, seed=k + 3, device=gpu)
     fac = ops.quantize_fp8(
         torch.randn(250, k, generator=torch.Generator().manual_seed(2))
         * 0.5).to(gpu)
     import flink_ms_amd._hip_ops as hip
     out8 = torch.empty(csr.num_rows, k, dtype=torch.uint8, device=gpu)
-    out_wp = torch.empty(csr.num_rows, k, dtype=torch.float32, device=gpu)
-    _e = torch.empty(0, device=gpu)
-    # wave-quad kernel invoked directly (kept as a measured ablation — the
-    # block-fused kernel won the k>64 shootout, gpu_debug/k128_variants.py)
-    hip.als_solve_wavefused2(csr.indptr, csr.indices, csr.values, fac,
-                             out_wp, out8, _e, 0.6,
-                             torch.cuda.current_stream().cuda_stream)
-    out_bl = ops.als_solve_side(csr, fac, reg=0.6, fused=True)
+    out_bl = ops.als_solve_side(csr, fac, reg=0.6, out_fp8=out8, fused=True)
     cpu_csr = csr.to("cpu")
     pair_csr = CSR(cpu_csr.indptr, cpu_csr.indices,
                    ops.fp8_rating_pair(cpu_csr.values),
@@ -415,18 +420,16 @@ def test_wavefused2_matches_block_fused(gpu, k):
                                      ops.dequantize_fp8(fac.cpu()), reg=0.6)
     torch.cuda.synchronize()
     scale = max(1.0, float(ref.abs().amax()))
-    err_wp = (out_wp.cpu() - ref).abs().amax() / scale
     err_bl = (out_bl.cpu() - ref).abs().amax() / scale
-    assert err_wp < 5e-3, f"wave-pair vs reference: {err_wp}"
     assert err_bl < 5e-3, f"block-fused vs reference: {err_bl}"
-    assert torch.equal(out8.cpu(), ops.quantize_fp8(out_wp.cpu()))
+    assert torch.equal(out8.cpu(), ops.quantize_fp8(out_bl.cpu()))
     # empty row + odd nrows tail
     indptr = torch.tensor([0, 0, csr.nnz, csr.nnz], dtype=torch.int64,
                           device=gpu)
     out3 = torch.empty(3, k, dtype=torch.float32, device=gpu)
     e = torch.empty(0, device=gpu)
-    hip.als_solve_wavefused2(indptr, csr.indices, csr.values, fac, out3,
-                             e, e, 0.6, torch.cuda.current_stream().cuda_stream)
+    hip.als_solve_fused(indptr, csr.indices, csr.values, fac, out3, e, e, e,
+                        0.6, torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     assert out3[0].abs().sum() == 0 and out3[2].abs().sum() == 0
     assert torch.isfinite(out3[1]).all()

@@ -105,17 +105,6 @@ def _call_wavefused(fn):
     return call
 
 
-def _call_wavefused2(a, st):
-    hip.als_solve_wavefused2(a["indptr"], a["indices"], a["values"],
-                             a["factors"], a["out_f32"], a["out_fp8"],
-                             a["row_order"], 0.3, st)
-
-
-def _wavefused2_args(device):
-    a = _als_args(device, True, k=80)
-    return _pick(a, *_CSR, "out_f32", "out_fp8", "row_order")
-
-
 def _gramian_args(device):
     a = _als_args(device, fp8=False)
     a = dict(_pick(a, *_CSR, "row_order"), b_out=a["out_f32"])
@@ -196,8 +185,6 @@ BINDINGS = {
     "als_solve_wavefused_db": (lambda d: _als_args(d, True),
                                _call_wavefused(hip.als_solve_wavefused_db),
                                _ALS_OUTS),
-    "als_solve_wavefused2": (_wavefused2_args, _call_wavefused2,
-                             ("out_f32", "out_fp8")),
     "gramian": (_gramian_args, _call_gramian, ("A_out", "b_out")),
     "dbg_gramian": (_dbg_gramian_args, _call_dbg_gramian,
                     ("A_out", "b_out", "blo")),
@@ -288,8 +275,7 @@ def test_cpu_wrong_dtypes_raise():
 
 @pytest.mark.parametrize("binding", ["als_solve_fused", "als_solve_fused[e4m3]",
                                      "als_solve_wavefused",
-                                     "als_solve_wavefused_db",
-                                     "als_solve_wavefused2"])
+                                     "als_solve_wavefused_db"])
 def test_cpu_too_few_output_rows(binding):
     """Shape checks read metadata only and run before the device check."""
     build, call, _ = BINDINGS[binding]
@@ -477,22 +463,25 @@ def test_gpu_variantless_call_runs_the_default(gpu, binding):
 
 
 @pytest.mark.gpu
-def test_gpu_wavefused2_accepts_a_taller_output(gpu):
-    """out_f32 may have more rows than the launch covers (the chunked path
-    scatters into full-side buffers): same rows as an exact-size call, the
-    extra rows untouched."""
-    k, degrees = 80, [0, 1, 33, 65]
+def test_gpu_wavefused_accepts_a_taller_output(gpu):
+    """The outputs may have more rows than the launch covers (the chunked
+    path scatters into full-side buffers with this kernel): same rows as an
+    exact-size call, the extra rows untouched."""
+    k, degrees = 64, [0, 1, 33, 65]
+    call = _call_wavefused(hip.als_solve_wavefused)
     exact = _als_args(gpu, True, k=k, degrees=degrees)
-    _call_wavefused2(exact, _stream())
+    call(exact, _stream())
     tall = _als_args(gpu, True, k=k, degrees=degrees)
-    tall["out_f32"], _, tall["out_fp8"] = _outs(gpu, len(degrees) + 2, k)
-    _call_wavefused2(tall, _stream())
+    tall["out_f32"], tall["out_bf16"], tall["out_fp8"] = _outs(
+        gpu, len(degrees) + 2, k)
+    call(tall, _stream())
     torch.cuda.synchronize()
     n = len(degrees)
-    for name in ("out_f32", "out_fp8"):
+    for name in _ALS_OUTS:
         assert torch.equal(_bits([tall[name][:n]])[0],
                            _bits([exact[name]])[0]), name
     assert (tall["out_f32"][n:] == SENTINEL).all()
+    assert (tall["out_bf16"][n:] == SENTINEL).all()
     assert (tall["out_fp8"][n:] == 0x7F).all()
     assert torch.isfinite(exact["out_f32"]).all()
     assert exact["out_f32"][0].abs().sum() == 0      # the degree-0 entity
