@@ -3,6 +3,10 @@
 Flags (ALSImpl.scala:22-62): --input, --fieldDelimiter (comma|tab, comma),
 --ignoreFirstLine (true), --iterations (10), --numFactors (10), --blocks,
 --temporaryPath, --lambda (0.9), --seed (42), --itemFactors, --userFactors.
+``--implicitPrefs`` (false) and ``--alpha`` (1.0) select confidence-weighted
+ALS for implicit feedback (Spark's flags of the same names): the rating
+column is an interaction strength, confidence 1 + alpha*|r|, preference
+[r > 0].  The model files keep their format.
 ``--blocks`` is accepted for CLI parity (blocking is GPU-count-driven).
 ``--temporaryPath <dir>`` stages each iteration's factors to disk in the
 model text format — the reference uses the flag to trade memory
@@ -42,6 +46,8 @@ def main(argv=None) -> int:
         num_factors=params.get_int("numFactors", 10),
         lambda_=params.get_float("lambda", 0.9),
         seed=params.get_int("seed", 42),
+        implicit_prefs=params.get_bool("implicitPrefs", False),
+        alpha=params.get_float("alpha", 1.0),
         dtype=torch.bfloat16 if ctx.device.type == "cuda" else torch.float32,
     )
     trainer = ALSTrainer(cfg, ctx)

@@ -61,6 +61,14 @@ class ALSConfig:
     # while exchanging block i+1").  'off' restores the serial exchange.
     overlap_exchange: str = 'auto'
     exchange_chunks: int = 4
+    # implicit feedback (Hu, Koren, Volinsky 2008; Spark's implicitPrefs):
+    # stored values are interaction strengths r (zero and negative legal),
+    # confidence c = 1 + alpha*|r|, preference p = [r > 0], and every
+    # unobserved pair counts with c = 1, p = 0 through the Gram matrix of
+    # the whole opposite side.  Regularisation stays the weighted-lambda
+    # lambda * n (n = stored entries of the row).
+    implicit_prefs: bool = False
+    alpha: float = 1.0
 
 
 @dataclass
@@ -167,6 +175,14 @@ class ALSTrainer:
             self.item_csr.indices = self.user_chunked.remap_indices(
                 self.item_csr.indices).to(dev)
 
+        # implicit feedback: per stored entry (scale, ext), once
+        self.user_w = self.item_w = None
+        if self.cfg.implicit_prefs:
+            self.user_w = ops.implicit_weights(self.user_csr.values,
+                                               self.cfg.alpha)
+            self.item_w = ops.implicit_weights(self.item_csr.values,
+                                               self.cfg.alpha)
+
         k = self.cfg.num_factors
         kp = ((k + 15) // 16) * 16 if dev.type == "cuda" else k
         self._kp = kp
@@ -236,10 +252,22 @@ class ALSTrainer:
         # the first user solve consumes the INITIAL item factors
         self.item_chunked.gather_all(self.item_shard, self._item_replica)
 
+    def _weighted_kw(self, side_w, other_shard) -> dict:
+        """Keyword arguments of a weighted (implicit-feedback) solve: the
+        side's (scale, ext) and base = Y^T Y over ALL rows of the opposite
+        side -- the Gram matrix of this rank's low-precision shard (padded
+        rows are zero) summed over ranks, so it never needs the replica and
+        is the same in every exchange mode.  Empty for explicit ratings."""
+        if side_w is None:
+            return {}
+        base = self.ctx.all_reduce_(ops.factor_gram(other_shard))
+        return {"scale": side_w[0], "ext": side_w[1], "base": base}
+
     def _solve_side_overlapped(self, csr, replica_in, out_f32, shard,
-                               chunk_ids, chunked) -> None:
+                               chunk_ids, chunked, kw) -> None:
         """Solve one side slab-by-slab; each finished slab leaves over
-        xGMI on the comm stream while the next slab computes."""
+        xGMI on the comm stream while the next slab computes.  ``kw``: the
+        weighted-solve arguments (``_weighted_kw``)."""
         ctx = self.ctx
         on_gpu = ctx.device.type == "cuda"
         fp8 = self._fp8
@@ -252,7 +280,7 @@ class ALSTrainer:
                     shard if fp8 else None,
                     shard if (on_gpu and not fp8
                               and shard.dtype == torch.bfloat16) else None,
-                    ids)
+                    ids, **kw)
                 if not on_gpu and not fp8:
                     a, b = int(ids[0]), int(ids[-1]) + 1
                     shard[a:b, : self.cfg.num_factors] = (
@@ -275,12 +303,16 @@ class ALSTrainer:
         self._replica_out = self._user_replica
         self._solve_side_overlapped(self.user_csr, self._item_replica,
                                     self._user_out, self.user_shard,
-                                    self._user_chunk_ids, self.user_chunked)
+                                    self._user_chunk_ids, self.user_chunked,
+                                    self._weighted_kw(self.user_w,
+                                                      self.item_shard))
         self.user_f32 = self._user_out
         self._replica_out = self._item_replica
         self._solve_side_overlapped(self.item_csr, self._user_replica,
                                     self._item_out, self.item_shard,
-                                    self._item_chunk_ids, self.item_chunked)
+                                    self._item_chunk_ids, self.item_chunked,
+                                    self._weighted_kw(self.item_w,
+                                                      self.user_shard))
         self.item_f32 = self._item_out
 
     # -- iteration -------------------------------------------------------
@@ -316,7 +348,8 @@ class ALSTrainer:
             if bf16_out else None,
             out_fp8=self.user_shard[: self.user_csr.num_rows]
             if fp8 else None,
-            row_order=self.user_order if on_gpu else None)
+            row_order=self.user_order if on_gpu else None,
+            **self._weighted_kw(self.user_w, self.item_shard))
         if not direct_out:
             self.user_shard[: self.user_csr.num_rows, : self.cfg.num_factors] = (
                 self.user_f32[:, : self.cfg.num_factors].to(self.cfg.dtype))
@@ -330,7 +363,8 @@ class ALSTrainer:
             if bf16_out else None,
             out_fp8=self.item_shard[: self.item_csr.num_rows]
             if fp8 else None,
-            row_order=self.item_order if on_gpu else None)
+            row_order=self.item_order if on_gpu else None,
+            **self._weighted_kw(self.item_w, self.user_shard))
         if not direct_out:
             self.item_shard[: self.item_csr.num_rows, : self.cfg.num_factors] = (
                 self.item_f32[:, : self.cfg.num_factors].to(self.cfg.dtype))

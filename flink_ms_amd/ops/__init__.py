@@ -88,7 +88,57 @@ def fp8_rating_pair(r: torch.Tensor) -> torch.Tensor:
     return hi + lo
 
 
+def bf16_rating_pair(r: torch.Tensor) -> torch.Tensor:
+    """The bf16 twin of :func:`fp8_rating_pair`: the bf16 hi/lo EXT pair of
+    the bf16 Gramian, dequantized (relative error ~2^-17)."""
+    return reference.rating_pair(r, "bf16")
+
+
 # -------------------------------------------------------------------- ALS
+
+def implicit_weights(values: torch.Tensor, alpha: float
+                     ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-entry ``(scale, ext)`` of confidence-weighted (implicit-feedback)
+    ALS for the weighted solves, computed once at setup in fp32 torch:
+    ``w = alpha*|r|``, ``scale = sqrt(w)``, ``ext = (1 + w) / scale`` where
+    ``r > 0`` else 0 (``w == 0`` gives 0, 0).  With ``base`` = the Gram
+    matrix of ALL opposite-side factors this makes the weighted solve the
+    Hu-Koren-Volinsky update.  Kernels and references both take the two
+    tensors as given: no square root is ever taken in a kernel."""
+    return reference.implicit_weights_reference(values, alpha)
+
+
+def _weights(scale, ext, base, nnz: int, k: int):
+    """Validate the (scale, ext, base) triple of a weighted solve: all three
+    or none.  Returns None (explicit path) or the triple."""
+    given = [t is not None for t in (scale, ext, base)]
+    if not any(given):
+        return None
+    if not all(given):
+        raise ValueError("scale, ext and base go together: pass all three "
+                         "(weighted normal equations) or none")
+    if scale.dim() != 1 or ext.dim() != 1 or scale.numel() != nnz \
+            or ext.numel() != nnz:
+        raise ValueError(f"scale and ext must be 1-D with one element per "
+                         f"stored entry ({nnz})")
+    if base.dim() != 2 or base.shape[0] != k or base.shape[1] != k:
+        raise ValueError(f"base must be [{k}][{k}], got {tuple(base.shape)}")
+    return scale, ext, base
+
+
+def _gpu_weights(w, kp: int):
+    """fp32 contiguous scale / ext and the base matrix zero-padded to the
+    kernels' [kp][kp]."""
+    scale, ext, base = w
+    base = base.to(torch.float32)
+    k = base.shape[0]
+    if k != kp:
+        padded = torch.zeros(kp, kp, dtype=torch.float32, device=base.device)
+        padded[:k, :k] = base
+        base = padded
+    return (scale.to(torch.float32).contiguous(),
+            ext.to(torch.float32).contiguous(), base.contiguous())
+
 
 # Lane-broadcast variants of the k<=64 register LDL (WREG_BC_* in
 # als_kernels.hip).  All of them compute bit-identical results; the
@@ -110,14 +160,26 @@ def _wreg_broadcast() -> int:
 
 
 def _launch_fused(ops, indptr, csr: CSR, fac, out, ob, o8, ro, reg,
-                  block: bool, allow_db: bool = False) -> None:
+                  block: bool, allow_db: bool = False, w=None) -> None:
     """Launch the fused Gramian+solve kernel for ``fac``'s rank and dtype:
     the wave-fused kernel for k <= 64, the block-fused kernel for k > 64 or
     ``block=True``.  ``indptr`` bounds the launch (nrows = len - 1); ``ob``
     / ``o8`` / ``ro`` are the optional bf16 / e4m3 images and launch
     schedule (empty = absent).  The block kernel writes only the image of
-    the gather dtype."""
+    the gather dtype.  ``w`` = (scale, ext, base) selects the weighted twins
+    (default broadcast level only)."""
     fp8 = fac.dtype == torch.uint8
+    if w is not None:
+        args = (indptr, csr.indices, *w, fac, out)
+        if block or fac.shape[1] > 64:
+            none = _empty(fac.device)
+            ops.als_solve_fused_w(*args, none if fp8 else ob,
+                                  o8 if fp8 else none, ro, float(reg),
+                                  _stream())
+        else:
+            ops.als_solve_wavefused_w(*args, ob, o8, ro, float(reg),
+                                      _stream())
+        return
     args = (indptr, csr.indices, csr.values, fac, out)
     if block or fac.shape[1] > 64:
         none = _empty(fac.device)
@@ -139,6 +201,10 @@ def als_solve_side(
     row_order: Optional[torch.Tensor] = None,
     fused: bool = False,
     slab_rows: Optional[int] = None,
+    *,
+    scale: Optional[torch.Tensor] = None,
+    ext: Optional[torch.Tensor] = None,
+    base: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """One ALS half-iteration: solve every row entity of ``csr`` against the
     opposite side's factors.  Returns fp32 [num_rows, k]; optionally also
@@ -157,7 +223,15 @@ def als_solve_side(
     ``other_factors`` dtype selects the gather precision: uint8 = e4m3
     bytes (one cache line per k<=64 row — the flagship path), anything
     else is cast to bf16.
+
+    ``scale`` / ``ext`` / ``base`` (all three or none): the weighted normal
+    equations of implicit-feedback ALS -- per stored entry a row scale and
+    an EXT value (:func:`implicit_weights`), and the [k][k] base matrix
+    (:func:`factor_gram` of the whole opposite side).  ``csr.values`` is
+    not read then.  ``None`` is the explicit path, untouched.
     """
+    w = _weights(scale, ext, base, csr.indices.numel(),
+                 other_factors.shape[1])
     if other_factors.is_cuda:
         ops = _require_hip()
         fp8 = other_factors.dtype == torch.uint8
@@ -172,6 +246,8 @@ def als_solve_side(
         o8 = out_fp8 if out_fp8 is not None else _empty(fac.device)
         ro = row_order if row_order is not None else _empty(fac.device)
         korig = other_factors.shape[1]
+        if w is not None:
+            w = _gpu_weights(w, k)
         if fused or k > 64 or slab_rows is None:
             # block-fused for k > 64 (and explicit fused=True), else the
             # k<=64 default: wave-fused Gramian+LDL — one wave per entity,
@@ -181,7 +257,7 @@ def als_solve_side(
             out = torch.empty(csr.num_rows, k, dtype=torch.float32,
                               device=fac.device)
             _launch_fused(ops, csr.indptr, csr, fac, out, ob, o8, ro, reg,
-                          block=fused, allow_db=True)
+                          block=fused, allow_db=True, w=w)
         else:
             # slab the normal equations: A is nrows*k*k fp32, which at the
             # 1B-rating configs would exceed HBM if materialized whole.
@@ -207,8 +283,13 @@ def als_solve_side(
             for s in range(0, csr.num_rows, slab):
                 e = min(s + slab, csr.num_rows)
                 As, bs = A[: e - s], b[: e - s]
-                ops.gramian(csr.indptr[s:e + 1], csr.indices, csr.values,
-                            fac, As, bs, use_ro, float(reg), _stream())
+                if w is not None:
+                    ops.gramian_w(csr.indptr[s:e + 1], csr.indices, *w, fac,
+                                  As, bs, use_ro, float(reg), _stream())
+                else:
+                    ops.gramian(csr.indptr[s:e + 1], csr.indices,
+                                csr.values, fac, As, bs, use_ro, float(reg),
+                                _stream())
                 obs = ob[s:e] if ob.numel() > 0 else ob
                 o8s = o8[s:e] if o8.numel() > 0 else o8
                 if k <= 64:
@@ -221,6 +302,14 @@ def als_solve_side(
                     if out_fp8 is not None:
                         out_fp8[s:e].copy_(quantize_fp8(out[s:e]))
         return out[:, :korig] if korig != k else out
+    if w is not None:                        # CPU: the weighted reference
+        out = reference.als_solve_weighted_reference(
+            csr, other_factors, reg, *w)
+        if out_fp8 is not None:
+            out_fp8.copy_(quantize_fp8(out[:, : out_fp8.shape[1]]))
+        if out_bf16 is not None:
+            out_bf16.copy_(out[:, : out_bf16.shape[1]].to(torch.bfloat16))
+        return out
     if other_factors.dtype == torch.uint8:   # CPU fp8 emulation
         out = reference.als_solve_side_reference(
             csr, dequantize_fp8(other_factors), reg)
@@ -238,12 +327,19 @@ def als_solve_chunk(
     out_fp8: Optional[torch.Tensor],
     out_bf16: Optional[torch.Tensor],
     entity_ids: torch.Tensor,
+    *,
+    scale: Optional[torch.Tensor] = None,
+    ext: Optional[torch.Tensor] = None,
+    base: Optional[torch.Tensor] = None,
 ) -> None:
     """Solve ONE slab of row entities (``entity_ids``) into the FULL-side
     output buffers (scatter by entity id through the kernels' row_order
     argument).  This is the building block of the overlapped C1 exchange:
     the trainer solves slab i while slab i-1's factors are already in
-    flight over xGMI (SURVEY.md §7 hard part)."""
+    flight over xGMI (SURVEY.md §7 hard part).  ``scale`` / ``ext`` /
+    ``base``: the weighted solve, as in :func:`als_solve_side`."""
+    w = _weights(scale, ext, base, csr.indices.numel(),
+                 other_factors.shape[1])
     if other_factors.is_cuda:
         ops = _require_hip()
         fp8 = other_factors.dtype == torch.uint8
@@ -256,8 +352,10 @@ def als_solve_chunk(
         # row_order-driven launch needs indptr[0:nrows+1] only for bounds;
         # pass a view sized to the slab so nrows = len(ids)
         ip = sub_indptr[: ids.numel() + 1]
+        if w is not None:
+            w = _gpu_weights(w, fac.shape[1])
         _launch_fused(ops, ip, csr, fac, out_f32, ob, o8, ids, reg,
-                      block=False)
+                      block=False, w=w)
         return
     # CPU (gloo tests): contiguous id range sliced out of the CSR
     a = int(entity_ids.min()) if entity_ids.numel() else 0
@@ -265,10 +363,14 @@ def als_solve_chunk(
     nnz0, nnz1 = int(csr.indptr[a]), int(csr.indptr[b])
     sub = CSR(csr.indptr[a:b + 1] - nnz0, csr.indices[nnz0:nnz1],
               csr.values[nnz0:nnz1], b - a, csr.num_cols)
-    fac32 = (dequantize_fp8(other_factors)
-             if other_factors.dtype == torch.uint8
-             else other_factors.to(torch.float32))
-    out = reference.als_solve_side_reference(sub, fac32, reg)
+    if w is not None:
+        out = reference.als_solve_weighted_reference(
+            sub, other_factors, reg, w[0][nnz0:nnz1], w[1][nnz0:nnz1], w[2])
+    else:
+        fac32 = (dequantize_fp8(other_factors)
+                 if other_factors.dtype == torch.uint8
+                 else other_factors.to(torch.float32))
+        out = reference.als_solve_side_reference(sub, fac32, reg)
     out_f32[a:b] = out
     if out_fp8 is not None:
         out_fp8[a:b] = quantize_fp8(out[:, : out_fp8.shape[1]])
@@ -276,9 +378,15 @@ def als_solve_chunk(
         out_bf16[a:b] = out[:, : out_bf16.shape[1]].to(torch.bfloat16)
 
 
-def gramian(csr: CSR, factors: torch.Tensor, reg: float) -> Tuple[torch.Tensor, torch.Tensor]:
+def gramian(csr: CSR, factors: torch.Tensor, reg: float, *,
+            scale: Optional[torch.Tensor] = None,
+            ext: Optional[torch.Tensor] = None,
+            base: Optional[torch.Tensor] = None,
+            ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Standalone K1 (parity tests / modular path).  ``factors`` as uint8 =
-    e4m3 bytes -> the fp8 gather kernel; else bf16."""
+    e4m3 bytes -> the fp8 gather kernel; else bf16.  ``scale`` / ``ext`` /
+    ``base``: the weighted normal equations, as in :func:`als_solve_side`."""
+    w = _weights(scale, ext, base, csr.indices.numel(), factors.shape[1])
     if factors.is_cuda:
         ops = _require_hip()
         fp8 = factors.dtype == torch.uint8
@@ -287,15 +395,59 @@ def gramian(csr: CSR, factors: torch.Tensor, reg: float) -> Tuple[torch.Tensor, 
         k = fac.shape[1]
         A = torch.empty(csr.num_rows, k, k, dtype=torch.float32, device=fac.device)
         b = torch.empty(csr.num_rows, k, dtype=torch.float32, device=fac.device)
-        ops.gramian(csr.indptr, csr.indices, csr.values, fac, A, b,
-                    _empty(fac.device), float(reg), _stream())
+        if w is not None:
+            ops.gramian_w(csr.indptr, csr.indices, *_gpu_weights(w, k), fac,
+                          A, b, _empty(fac.device), float(reg), _stream())
+        else:
+            ops.gramian(csr.indptr, csr.indices, csr.values, fac, A, b,
+                        _empty(fac.device), float(reg), _stream())
         korig = factors.shape[1]
         if korig != k:
             return A[:, :korig, :korig], b[:, :korig]
         return A, b
+    if w is not None:
+        return reference.gramian_weighted_reference(csr, factors, reg, *w)
     if factors.dtype == torch.uint8:
         return reference.gramian_reference(csr, dequantize_fp8(factors), reg)
     return reference.gramian_reference(csr, factors, reg)
+
+
+def factor_gram(factors: torch.Tensor,
+                rows_per_part: Optional[int] = None) -> torch.Tensor:
+    """``G = F^T F`` [k][k] fp32 over every row of a factor table: the base
+    matrix of the implicit-feedback solves.  On the GPU the table is read
+    as stored (uint8 = e4m3 bytes, else bf16; e4m3 is widened exactly to
+    bf16 in staging) and contracted by the bf16 MFMA; per-wave partial sums over ``rows_per_part`` rows (``None`` =
+    the launcher's choice, see :func:`factor_gram_rows_per_part`) are added
+    in a fixed order, so the result is bit-reproducible and exactly
+    symmetric; it depends on ``rows_per_part`` only within fp32 rounding.
+    Ranks up to 128."""
+    if factors.dim() != 2:
+        raise ValueError("factors must be 2-D")
+    if factors.is_cuda:
+        ops = _require_hip()
+        fp8 = factors.dtype == torch.uint8
+        if fp8:
+            fac = factors.contiguous()
+            if fac.shape[1] % 16:
+                raise ValueError("fp8 factor image must be 16-col padded")
+        else:
+            fac = _pad_k(factors.to(torch.bfloat16).contiguous())
+        k, korig = fac.shape[1], factors.shape[1]
+        if k > 128:
+            raise ValueError(f"factor_gram handles rank <= 128, got {korig}")
+        if fac.shape[0] == 0:
+            return torch.zeros(korig, korig, dtype=torch.float32,
+                               device=fac.device)
+        G = ops.factor_gram(fac, int(rows_per_part or 0), _stream())
+        return G[:korig, :korig] if korig != k else G
+    return reference.factor_gram_reference(factors)
+
+
+def factor_gram_rows_per_part(n: int, k: int) -> int:
+    """Rows per part a GPU ``factor_gram`` over an [n][k] table uses when
+    ``rows_per_part`` is not given (k the 16-padded rank)."""
+    return int(_require_hip().factor_gram_rows_per_part(int(n), int(k)))
 
 
 def cholesky_solve(A: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

@@ -57,7 +57,16 @@
 // FP8 selects the gather precision and, with it, the low-precision image of
 // the solution written beside out_f32 for the next half-iteration (bf16
 // words or e4m3 bytes; out_lowp may be null).
-template <int KT, bool FP8>
+//
+// WT (every Gramian kernel below): the weighted normal equations of
+// confidence-weighted (implicit-feedback) ALS,
+//   A = G0 + sum_j row~_j row~_j^T + reg*n*I,  b = sum_j pair(ext_j) row~_j,
+//   row~_j = round_D(scale_j * F[indices_j]),
+// with ``values`` carrying ext[], ``scale`` the per-rating sqrt-weights and
+// ``G0`` the symmetric [K][K] fp32 base matrix (lower triangle read).  The
+// WT = false instantiations ignore scale / G0 (null) and compile to what
+// they compiled to before the flag existed.
+template <int KT, bool FP8, bool WT = false>
 __launch_bounds__(256)
 // waves_per_eu(3): without it the allocator splits 93 VGPR + 88 AGPR
 // (181 total -> 2 waves/SIMD); constrained it finds a 127-VGPR, zero-AGPR,
@@ -70,7 +79,8 @@ __global__ void k_als_solve_fused(
     const typename GatherT<FP8>::elem* __restrict__ factors,
     float* __restrict__ out_f32,
     typename GatherT<FP8>::elem* __restrict__ out_lowp,
-    const int* __restrict__ row_order, long long nrows, float reg) {
+    const int* __restrict__ row_order, long long nrows, float reg,
+    const float* __restrict__ scale, const float* __restrict__ G0) {
     constexpr int K = Geo<KT>::K;
     __shared__ __align__(16) char
         smem[FP8 ? Geo<KT>::SMEM8_TRI : Geo<KT>::SMEM_TRI];
@@ -78,8 +88,8 @@ __global__ void k_als_solve_fused(
     if (row >= nrows) return;
     if (row_order) row = row_order[row];
 
-    const int n = gramian_to_lds<KT, true, true, FP8>(
-        smem, indptr, indices, values, factors, row, reg);
+    const int n = gramian_to_lds<KT, true, true, FP8, WT>(
+        smem, indptr, indices, values, factors, row, reg, scale, G0);
     if (n == 0) { write_zero_row<KT>(out_f32, out_lowp, row); return; }
 
     float* A = (float*)smem;
@@ -100,7 +110,7 @@ __global__ void k_als_solve_fused(
 // processes entity row_order[i] and writes A_out/b_out at THAT row, so the
 // downstream batched solve stays order-agnostic (heavy entities launch
 // first; avoids tail stragglers at the end of the grid).
-template <int KT, bool FP8>
+template <int KT, bool FP8, bool WT = false>
 __launch_bounds__(256)
 __global__ void k_gramian(
     const long long* __restrict__ indptr, const int* __restrict__ indices,
@@ -108,7 +118,8 @@ __global__ void k_gramian(
     const typename GatherT<FP8>::elem* __restrict__ factors,
     float* __restrict__ A_out,   // [nrows][K][K]
     float* __restrict__ b_out,   // [nrows][K]
-    const int* __restrict__ row_order, long long nrows, float reg) {
+    const int* __restrict__ row_order, long long nrows, float reg,
+    const float* __restrict__ scale, const float* __restrict__ G0) {
     constexpr int K = Geo<KT>::K;
     __shared__ __align__(16) char smem[FP8 ? Geo<KT>::SMEM8 : Geo<KT>::SMEM];
     long long row = blockIdx.x;
@@ -116,12 +127,18 @@ __global__ void k_gramian(
     if (row_order) row = row_order[row];
     const int tid = threadIdx.x;
 
-    const int n = gramian_to_lds<KT, true, false, FP8>(
-        smem, indptr, indices, values, factors, row, reg);
+    const int n = gramian_to_lds<KT, true, false, FP8, WT>(
+        smem, indptr, indices, values, factors, row, reg, scale, G0);
     float* A = (float*)smem;
     float* b = A + K * (K + 1);
     if (n == 0) {
-        for (int i = tid; i < K * K; i += 256) A_out[row * K * K + i] = 0.0f;
+        // weighted: an empty sum leaves A = G0 (and b = 0, so x = 0)
+        for (int i = tid; i < K * K; i += 256) {
+            float a0 = 0.0f;
+            if constexpr (WT)
+                a0 = G0[max(i / K, i % K) * K + min(i / K, i % K)];
+            A_out[row * K * K + i] = a0;
+        }
         for (int c = tid; c < K; c += 256) b_out[row * K + c] = 0.0f;
         return;
     }
@@ -1033,7 +1050,30 @@ __global__ void k_als_solve_wavefused_db(const long long* __restrict__ indptr,
     }
 }
 
-template <int KT, bool FP8, int BC>
+// T[] = the lower tiles of the symmetric base matrix G0 ([K][K] fp32), in
+// the C-fragment layout the LDL consumes (row 16I + 4*g4 + r, column
+// 16J + li): wreg_load_A's map, with the diagonal tiles reading
+// G0[max][min] so that nothing above the diagonal is touched.
+template <int KT, int t = 0>
+DEV_INLINE void wavefused_load_base(f32x4* T, const float* __restrict__ G0,
+                                    int g4, int li) {
+    if constexpr (t < KT * (KT + 1) / 2) {
+        constexpr int K = KT * 16;
+        constexpr int I = lo_tile_i(t);
+        constexpr int J = t - (I * (I + 1)) / 2;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = I * 16 + g4 * 4 + r, col = J * 16 + li;
+            if constexpr (I == J)
+                T[t][r] = G0[max(row, col) * K + min(row, col)];
+            else
+                T[t][r] = G0[row * K + col];
+        }
+        wavefused_load_base<KT, t + 1>(T, G0, g4, li);
+    }
+}
+
+template <int KT, bool FP8, int BC, bool WT = false>
 __launch_bounds__(256)
 // waves_per_eu(5): 96 VGPRs with ~12-17 spilled (52-60 B/lane scratch) buys
 // a 5th wave/SIMD over the natural 105-reg allocation — measured 3.23 ->
@@ -1050,7 +1090,9 @@ __global__ void k_als_solve_wavefused(const long long* __restrict__ indptr,
                                       unsigned short* __restrict__ out_bf16,
                                       unsigned char* __restrict__ out_fp8,
                                       const int* __restrict__ row_order,
-                                      long long nrows, float reg) {
+                                      long long nrows, float reg,
+                                      const float* __restrict__ scale,
+                                      const float* __restrict__ G0) {
     constexpr int K = KT * 16;
     static_assert(K <= 64, "wave-fused path handles k <= 64");
     constexpr int NA = KT * (KT + 1) / 2;
@@ -1094,8 +1136,12 @@ __global__ void k_als_solve_wavefused(const long long* __restrict__ indptr,
         }
     }
     f32x4 T[NA], E[KT];
+    if constexpr (WT) {
+        wavefused_load_base<KT>(T, G0, g4, li);
+    } else {
 #pragma unroll
-    for (int t = 0; t < NA; ++t) T[t] = f32x4{0, 0, 0, 0};
+        for (int t = 0; t < NA; ++t) T[t] = f32x4{0, 0, 0, 0};
+    }
 #pragma unroll
     for (int p = 0; p < KT; ++p) E[p] = f32x4{0, 0, 0, 0};
     const int nchunks = (n + 31) >> 5;
@@ -1104,14 +1150,15 @@ __global__ void k_als_solve_wavefused(const long long* __restrict__ indptr,
             const int sub = (lane >= NT) ? 1 : 0;
             const int lch = ch + sub;
             if (lch < nchunks && lane < 2 * NT)
-                stage_chunk_w<KT, FP8, NT>(buf + sub * SB, indices, values,
-                                           factors,
-                                           p0 + (long long)lch * 32,
-                                           n - lch * 32, lane - sub * NT);
+                stage_chunk_w<KT, FP8, NT, WT>(buf + sub * SB, indices,
+                                               values, factors,
+                                               p0 + (long long)lch * 32,
+                                               n - lch * 32, lane - sub * NT,
+                                               scale);
         } else {
-            stage_chunk_w<KT, FP8>(buf, indices, values, factors,
-                                   p0 + (long long)ch * 32, n - ch * 32,
-                                   lane);
+            stage_chunk_w<KT, FP8, WAVE, WT>(buf, indices, values, factors,
+                                             p0 + (long long)ch * 32,
+                                             n - ch * 32, lane, scale);
         }
         WREG_FENCE();                  // cross-lane LDS write -> read
         {
@@ -1149,6 +1196,86 @@ __global__ void k_als_solve_wavefused(const long long* __restrict__ indptr,
         if (out_bf16) out_bf16[e * K + lane] = f2bf(x0);
         if (out_fp8) out_fp8[e * K + lane] = f2fp8(x0);
     }
+}
+
+// -------- factor Gram matrix G = F^T F (the implicit-feedback base) --------
+// F: a bf16 / e4m3 factor table [n][K].  One WAVE owns one part of
+// rows_per_part (a multiple of 32) consecutive rows: each 32-row chunk goes
+// through the transposed stage (stage_chunk_w<IDENT>) and the lower-tile
+// MFMAs of the wave-fused kernel, and the wave's partial lower tiles land
+// in ws[part][K][K].  k_factor_gram_reduce then sums the parts in part
+// order and mirrors the lower triangle: no floating-point atomics, so G is
+// bit-reproducible, and exactly symmetric.  Rows >= n stage as zeros.
+// An e4m3 table is widened to bf16 while staging (exact: every e4m3 value
+// is a bf16 value) and contracted by the bf16 MFMA: the fp8 MFMA sums its
+// 32 products with ~2^-17 relative precision (measured, docs/KERNELS.md),
+// short of the fp32 dot bound this matrix is held to -- it is added to
+// EVERY entity's normal equations.
+template <int KT, int t = 0>
+DEV_INLINE void factor_gram_store(const f32x4* T, float* dst, int g4, int li) {
+    if constexpr (t < KT * (KT + 1) / 2) {
+        constexpr int K = KT * 16;
+        constexpr int I = lo_tile_i(t);
+        constexpr int J = t - (I * (I + 1)) / 2;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            dst[(I * 16 + g4 * 4 + r) * K + J * 16 + li] = T[t][r];
+        factor_gram_store<KT, t + 1>(T, dst, g4, li);
+    }
+}
+
+template <int KT, bool FP8>
+__launch_bounds__(256)
+__global__ void k_factor_gram(
+    const typename GatherT<FP8>::elem* __restrict__ factors,
+    float* __restrict__ ws,      // [parts][K][K], lower tiles written
+    long long n, long long rows_per_part, long long parts) {
+    constexpr int K = KT * 16;
+    constexpr int NA = KT * (KT + 1) / 2;
+    constexpr int TROW = Geo<KT>::TROW;            // bf16 stage either way
+    constexpr int SB = ((K + 16) * TROW + 15) & ~15;
+    constexpr int FB = 16;
+    __shared__ __align__(16) char smem[4 * SB];
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const long long part = (long long)blockIdx.x * 4 + w;
+    if (part >= parts) return;
+    char* buf = smem + (long long)w * SB;
+    const int g4 = lane >> 4, li = lane & 15;
+    f32x4 T[NA];
+#pragma unroll
+    for (int t = 0; t < NA; ++t) T[t] = f32x4{0, 0, 0, 0};
+    const long long r0 = part * rows_per_part;
+    const long long r1 = min(n, r0 + rows_per_part);
+    for (long long base = r0; base < r1; base += 32) {
+        stage_chunk_w<KT, false, WAVE, false, true, FP8>(
+            buf, nullptr, nullptr, factors, base,
+            (int)min((long long)32, r1 - base), lane);
+        WREG_FENCE();                  // cross-lane LDS write -> read
+        bf16x8 frag[KT];
+#pragma unroll
+        for (int t = 0; t < KT; ++t)
+            frag[t] = *(const bf16x8*)(
+                buf + (long long)(t * 16 + li) * TROW + g4 * FB);
+        mfma_lower_tiles<KT, false>(frag, T);
+        WREG_FENCE();                  // reads drained before next stage
+    }
+    factor_gram_store<KT>(T, ws + part * (long long)(K * K), g4, li);
+}
+
+template <int KT>
+__launch_bounds__(256)
+__global__ void k_factor_gram_reduce(const float* __restrict__ ws,
+                                     float* __restrict__ G, long long parts) {
+    constexpr int K = KT * 16;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= K * K) return;
+    const int i = idx / K, j = idx % K;
+    if (i < j) return;                 // (i, j) is written from (j, i)
+    float acc = 0.0f;
+    for (long long p = 0; p < parts; ++p) acc += ws[p * (K * K) + idx];
+    G[i * K + j] = acc;
+    G[j * K + i] = acc;
 }
 
 // ------------------------------------------------------------- MFMA probes
@@ -1258,25 +1385,74 @@ extern "C" const char* fma_err_str(int err) {
     return hipGetErrorString((hipError_t)err);
 }
 
-extern "C" int fma_als_solve_fused(
+// WT = false: the explicit kernels (scale / base null); WT = true: the
+// weighted twins, ``values`` carrying ext[]
+template <bool WT>
+static int launch_als_solve_fused(
     int k, int fp8, const long long* indptr, const int* indices,
     const float* values, const void* factors, float* out_f32,
     unsigned short* out_bf16, unsigned char* out_fp8, const int* row_order,
-    long long nrows, float reg, void* stream) {
+    long long nrows, float reg, const float* scale, const float* base,
+    void* stream) {
     if (bad_shape(k, nrows) || (fp8 ? out_bf16 != nullptr : out_fp8 != nullptr))
         return hipErrorInvalidValue;
     return dispatch_ic<1, 2, 3, 4, 5, 6, 7, 8>(k / 16, [&](auto kt) {
         constexpr int KT = decltype(kt)::value;
         if (fp8)
-            k_als_solve_fused<KT, true>
+            k_als_solve_fused<KT, true, WT>
                 <<<grid_block(nrows), kBlock, 0, (hipStream_t)stream>>>(
                     indptr, indices, values, (const unsigned char*)factors,
-                    out_f32, out_fp8, row_order, nrows, reg);
+                    out_f32, out_fp8, row_order, nrows, reg, scale, base);
         else
-            k_als_solve_fused<KT, false>
+            k_als_solve_fused<KT, false, WT>
                 <<<grid_block(nrows), kBlock, 0, (hipStream_t)stream>>>(
                     indptr, indices, values, (const unsigned short*)factors,
-                    out_f32, out_bf16, row_order, nrows, reg);
+                    out_f32, out_bf16, row_order, nrows, reg, scale, base);
+        return hipGetLastError();
+    });
+}
+
+extern "C" int fma_als_solve_fused(
+    int k, int fp8, const long long* indptr, const int* indices,
+    const float* values, const void* factors, float* out_f32,
+    unsigned short* out_bf16, unsigned char* out_fp8, const int* row_order,
+    long long nrows, float reg, void* stream) {
+    return launch_als_solve_fused<false>(
+        k, fp8, indptr, indices, values, factors, out_f32, out_bf16, out_fp8,
+        row_order, nrows, reg, nullptr, nullptr, stream);
+}
+
+extern "C" int fma_als_solve_fused_w(
+    int k, int fp8, const long long* indptr, const int* indices,
+    const float* scale, const float* ext, const float* base,
+    const void* factors, float* out_f32, unsigned short* out_bf16,
+    unsigned char* out_fp8, const int* row_order, long long nrows, float reg,
+    void* stream) {
+    if (!scale || !ext || !base) return hipErrorInvalidValue;
+    return launch_als_solve_fused<true>(
+        k, fp8, indptr, indices, ext, factors, out_f32, out_bf16, out_fp8,
+        row_order, nrows, reg, scale, base, stream);
+}
+
+template <bool WT>
+static int launch_gramian(
+    int k, int fp8, const long long* indptr, const int* indices,
+    const float* values, const void* factors, float* A_out, float* b_out,
+    const int* row_order, long long nrows, float reg, const float* scale,
+    const float* base, void* stream) {
+    if (bad_shape(k, nrows)) return hipErrorInvalidValue;
+    return dispatch_ic<1, 2, 3, 4, 5, 6, 7, 8>(k / 16, [&](auto kt) {
+        constexpr int KT = decltype(kt)::value;
+        if (fp8)
+            k_gramian<KT, true, WT>
+                <<<grid_block(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                    indptr, indices, values, (const unsigned char*)factors,
+                    A_out, b_out, row_order, nrows, reg, scale, base);
+        else
+            k_gramian<KT, false, WT>
+                <<<grid_block(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                    indptr, indices, values, (const unsigned short*)factors,
+                    A_out, b_out, row_order, nrows, reg, scale, base);
         return hipGetLastError();
     });
 }
@@ -1285,21 +1461,20 @@ extern "C" int fma_gramian(
     int k, int fp8, const long long* indptr, const int* indices,
     const float* values, const void* factors, float* A_out, float* b_out,
     const int* row_order, long long nrows, float reg, void* stream) {
-    if (bad_shape(k, nrows)) return hipErrorInvalidValue;
-    return dispatch_ic<1, 2, 3, 4, 5, 6, 7, 8>(k / 16, [&](auto kt) {
-        constexpr int KT = decltype(kt)::value;
-        if (fp8)
-            k_gramian<KT, true>
-                <<<grid_block(nrows), kBlock, 0, (hipStream_t)stream>>>(
-                    indptr, indices, values, (const unsigned char*)factors,
-                    A_out, b_out, row_order, nrows, reg);
-        else
-            k_gramian<KT, false>
-                <<<grid_block(nrows), kBlock, 0, (hipStream_t)stream>>>(
-                    indptr, indices, values, (const unsigned short*)factors,
-                    A_out, b_out, row_order, nrows, reg);
-        return hipGetLastError();
-    });
+    return launch_gramian<false>(k, fp8, indptr, indices, values, factors,
+                                 A_out, b_out, row_order, nrows, reg, nullptr,
+                                 nullptr, stream);
+}
+
+extern "C" int fma_gramian_w(
+    int k, int fp8, const long long* indptr, const int* indices,
+    const float* scale, const float* ext, const float* base,
+    const void* factors, float* A_out, float* b_out, const int* row_order,
+    long long nrows, float reg, void* stream) {
+    if (!scale || !ext || !base) return hipErrorInvalidValue;
+    return launch_gramian<true>(k, fp8, indptr, indices, ext, factors, A_out,
+                                b_out, row_order, nrows, reg, scale, base,
+                                stream);
 }
 
 extern "C" int fma_cholesky_solve_ph(
@@ -1384,14 +1559,98 @@ extern "C" int fma_als_solve_wavefused(
                 k_als_solve_wavefused<KT, true, BC>
                     <<<grid_wave(nrows), kBlock, 0, (hipStream_t)stream>>>(
                         indptr, indices, values, factors, out_f32, out_bf16,
-                        out_fp8, row_order, nrows, reg);
+                        out_fp8, row_order, nrows, reg, nullptr, nullptr);
             else
                 k_als_solve_wavefused<KT, false, BC>
                     <<<grid_wave(nrows), kBlock, 0, (hipStream_t)stream>>>(
                         indptr, indices, values, factors, out_f32, out_bf16,
-                        out_fp8, row_order, nrows, reg);
+                        out_fp8, row_order, nrows, reg, nullptr, nullptr);
             return hipGetLastError();
         });
+    });
+}
+
+// weighted twin: the readlane broadcast level only (the other levels are
+// measured ablations of the explicit kernel)
+extern "C" int fma_als_solve_wavefused_w(
+    int k, int fp8, const long long* indptr, const int* indices,
+    const float* scale, const float* ext, const float* base,
+    const void* factors, float* out_f32, unsigned short* out_bf16,
+    unsigned char* out_fp8, const int* row_order, long long nrows, float reg,
+    void* stream) {
+    if (bad_shape(k, nrows) || !scale || !ext || !base)
+        return hipErrorInvalidValue;
+    return dispatch_ic<1, 2, 3, 4>(k / 16, [&](auto kt) {
+        constexpr int KT = decltype(kt)::value;
+        if (fp8)
+            k_als_solve_wavefused<KT, true, WREG_BC_HOIST, true>
+                <<<grid_wave(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                    indptr, indices, ext, factors, out_f32, out_bf16,
+                    out_fp8, row_order, nrows, reg, scale, base);
+        else
+            k_als_solve_wavefused<KT, false, WREG_BC_HOIST, true>
+                <<<grid_wave(nrows), kBlock, 0, (hipStream_t)stream>>>(
+                    indptr, indices, ext, factors, out_f32, out_bf16,
+                    out_fp8, row_order, nrows, reg, scale, base);
+        return hipGetLastError();
+    });
+}
+
+// ---- factor Gram.  rows_per_part = 0: the launcher's choice; otherwise
+// rounded up to a multiple of 32 (the stage chunk).
+namespace {
+inline long long factor_gram_rpp(long long n, int k, long long rows_per_part) {
+    if (rows_per_part > 0) return (rows_per_part + 31) / 32 * 32;
+    // enough parts to fill the machine, few enough that the workspace
+    // (parts * k * k fp32) stays a small fraction of the table
+    const long long max_parts = k <= 64 ? 1024 : 256;
+    const long long rpp = (n + max_parts - 1) / max_parts;
+    return rpp <= 32 ? 32 : (rpp + 31) / 32 * 32;
+}
+inline bool factor_gram_bad(long long n, int k, long long rows_per_part) {
+    return n <= 0 || k <= 0 || k % 16 != 0 || k > 128 || rows_per_part < 0;
+}
+}  // namespace
+
+extern "C" long long fma_factor_gram_rows_per_part(long long n, int k) {
+    if (factor_gram_bad(n, k, 0)) return -1;
+    return factor_gram_rpp(n, k, 0);
+}
+
+extern "C" long long fma_factor_gram_workspace_bytes(long long n, int k,
+                                                     long long rows_per_part) {
+    if (factor_gram_bad(n, k, rows_per_part)) return -1;
+    const long long rpp = factor_gram_rpp(n, k, rows_per_part);
+    return (n + rpp - 1) / rpp * (long long)k * k * 4;
+}
+
+extern "C" int fma_factor_gram(int k, int fp8, const void* factors,
+                               long long n, long long rows_per_part,
+                               float* G, void* workspace,
+                               long long workspace_bytes, void* stream) {
+    const long long need = fma_factor_gram_workspace_bytes(n, k, rows_per_part);
+    if (need < 0 || workspace_bytes < need || !workspace)
+        return hipErrorInvalidValue;
+    const long long rpp = factor_gram_rpp(n, k, rows_per_part);
+    const long long parts = (n + rpp - 1) / rpp;
+    return dispatch_ic<1, 2, 3, 4, 5, 6, 7, 8>(k / 16, [&](auto kt) {
+        constexpr int KT = decltype(kt)::value;
+        if (fp8)
+            k_factor_gram<KT, true>
+                <<<grid_wave(parts), kBlock, 0, (hipStream_t)stream>>>(
+                    (const unsigned char*)factors, (float*)workspace, n, rpp,
+                    parts);
+        else
+            k_factor_gram<KT, false>
+                <<<grid_wave(parts), kBlock, 0, (hipStream_t)stream>>>(
+                    (const unsigned short*)factors, (float*)workspace, n, rpp,
+                    parts);
+        hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+        k_factor_gram_reduce<KT>
+            <<<dim3((k * k + 255) / 256), kBlock, 0, (hipStream_t)stream>>>(
+                (const float*)workspace, G, parts);
+        return hipGetLastError();
     });
 }
 

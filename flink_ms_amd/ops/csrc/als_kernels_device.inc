@@ -89,12 +89,82 @@ DEV_INLINE constexpr int lo_tile_i(int t) {
 // 4x16B row pieces (a whole k<=64 e4m3 row is ONE 16-B load x4 lanes) and
 // writes 16 ds_write_b32 transposed columns.  nrem = ratings left in the
 // entity (rows >= nrem zero-filled).
-template <int KT, bool FP8, int NLANES = WAVE>
+//
+// WT (weighted normal equations, docs/KERNELS.md "Implicit feedback"): each
+// gathered row is rescaled by its rating's scale[] entry between the gather
+// and the transpose -- dequantise, ONE fp32 multiply, round back to the
+// gather dtype (RNE) -- and ``values`` carries ext[] for the EXT rows.  The
+// scale address depends on the rating's position only, so its load issues
+// with the index loads: one 4-byte load per row piece, no second gather
+// round.  IDENT (k_factor_gram): the chunk is rows base.. of the table
+// itself (no index list, no EXT rows).  WIDEN (bf16 stage only): the table
+// holds e4m3 bytes, widened exactly to bf16 as they are gathered.
+
+typedef float stage_f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 stage_bf16x2 __attribute__((ext_vector_type(2)));
+
+// e4m3 saturation of f2fp8 (finite values clamp to +-448, NaN/inf pass)
+DEV_INLINE float stage_fp8_sat(float x) {
+    const unsigned u = __builtin_bit_cast(unsigned, x);
+    return (u & 0x7f800000u) != 0x7f800000u
+               ? __builtin_amdgcn_fmed3f(x, 448.0f, -448.0f) : x;
+}
+
+// four e4m3 bytes times s, re-rounded: per byte f2fp8(fp82f(b) * s)
+DEV_INLINE unsigned stage_rescale_fp8x4(unsigned w, float s) {
+    const stage_f32x2 s2 = {s, s};
+    stage_f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false) * s2;
+    stage_f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true) * s2;
+    int r = __builtin_amdgcn_cvt_pk_fp8_f32(stage_fp8_sat(lo.x),
+                                            stage_fp8_sat(lo.y), 0, false);
+    r = __builtin_amdgcn_cvt_pk_fp8_f32(stage_fp8_sat(hi.x),
+                                        stage_fp8_sat(hi.y), r, true);
+    return (unsigned)r;
+}
+
+// two bf16 words times s, re-rounded (RNE, v_cvt_pk_bf16_f32)
+DEV_INLINE unsigned stage_rescale_bf16x2(unsigned d, float s) {
+    const stage_f32x2 v = {__builtin_bit_cast(float, d << 16),
+                           __builtin_bit_cast(float, d & 0xffff0000u)};
+    const stage_f32x2 s2 = {s, s};
+    return __builtin_bit_cast(
+        unsigned, __builtin_convertvector(v * s2, stage_bf16x2));
+}
+
+// eight e4m3 bytes as eight bf16 words (exact), with the scalar helpers:
+// k_factor_gram is a small memory-bound pass
+DEV_INLINE uint4 stage_widen_fp8x8(uint2 raw) {
+    unsigned out[4];
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        const unsigned w = (h < 2 ? raw.x : raw.y) >> (16 * (h & 1));
+        out[h] = (unsigned)f2bf(fp82f((unsigned char)(w & 0xffu)))
+                 | ((unsigned)f2bf(fp82f((unsigned char)((w >> 8) & 0xffu)))
+                    << 16);
+    }
+    return uint4{out[0], out[1], out[2], out[3]};
+}
+
+template <bool FP8>
+DEV_INLINE uint4 stage_rescale_piece(uint4 x, float s) {
+    if constexpr (FP8)
+        return uint4{stage_rescale_fp8x4(x.x, s), stage_rescale_fp8x4(x.y, s),
+                     stage_rescale_fp8x4(x.z, s), stage_rescale_fp8x4(x.w, s)};
+    else
+        return uint4{stage_rescale_bf16x2(x.x, s),
+                     stage_rescale_bf16x2(x.y, s),
+                     stage_rescale_bf16x2(x.z, s),
+                     stage_rescale_bf16x2(x.w, s)};
+}
+
+template <int KT, bool FP8, int NLANES = WAVE, bool WT = false,
+          bool IDENT = false, bool WIDEN = false>
 DEV_INLINE void stage_chunk_w(char* buf,
                               const int* __restrict__ indices,
                               const float* __restrict__ values,
                               const void* __restrict__ factors_v,
-                              long long base, int nrem, int lane) {
+                              long long base, int nrem, int lane,
+                              const float* __restrict__ scale = nullptr) {
     constexpr int K = Geo<KT>::K;
     constexpr int TROW = FP8 ? Geo<KT>::TROW8 : Geo<KT>::TROW;
     if constexpr (FP8) {
@@ -103,16 +173,25 @@ DEV_INLINE void stage_chunk_w(char* buf,
         for (int t = lane; t < NT; t += NLANES) {
             const int q = t & 7, c16 = t >> 3;
             uint4 v[4];
+            [[maybe_unused]] float sc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 uint4 x = {0, 0, 0, 0};
                 const int row = 4 * q + m;
                 if (row < nrem) {
-                    const long long col = indices[base + row];
+                    long long col;
+                    if constexpr (IDENT) col = base + row;
+                    else col = indices[base + row];
                     x = *(const uint4*)(factors + col * (long long)K
                                         + c16 * 16);
+                    if constexpr (WT) sc[m] = scale[base + row];
                 }
                 v[m] = x;
+            }
+            if constexpr (WT) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+                    v[m] = stage_rescale_piece<FP8>(v[m], sc[m]);
             }
             char* rb = buf + (long long)(16 * c16) * TROW + q * 4;
 #pragma unroll
@@ -131,16 +210,30 @@ DEV_INLINE void stage_chunk_w(char* buf,
         for (int t = lane; t < NT; t += NLANES) {
             const int q = t & 7, c8 = t >> 3;
             uint4 v[4];
+            [[maybe_unused]] float sc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 uint4 x = {0, 0, 0, 0};
                 const int row = 4 * q + m;
                 if (row < nrem) {
-                    const long long col = indices[base + row];
-                    x = *(const uint4*)(factors + col * (long long)K
-                                        + c8 * 8);
+                    long long col;
+                    if constexpr (IDENT) col = base + row;
+                    else col = indices[base + row];
+                    if constexpr (WIDEN)
+                        x = stage_widen_fp8x8(*(const uint2*)(
+                            (const unsigned char*)factors_v
+                            + col * (long long)K + c8 * 8));
+                    else
+                        x = *(const uint4*)(factors + col * (long long)K
+                                            + c8 * 8);
+                    if constexpr (WT) sc[m] = scale[base + row];
                 }
                 v[m] = x;
+            }
+            if constexpr (WT) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+                    v[m] = stage_rescale_piece<FP8>(v[m], sc[m]);
             }
             char* rb = buf + (long long)(8 * c8) * TROW + q * 8;
 #pragma unroll
@@ -159,6 +252,7 @@ DEV_INLINE void stage_chunk_w(char* buf,
             }
         }
     }
+    if constexpr (IDENT) return;
     if (lane < 8) {  // rating hi/lo EXT rows K, K+1
         if constexpr (FP8) {
             unsigned h = 0, l = 0;
@@ -519,13 +613,19 @@ DEV_INLINE void solve_lds_block_tri(const float* A, const float* b,
 // lambda*n*I) + combined b in LDS.  Per round, wave w gathers chunk
 // r0 + w into its own stage buffer (NCH chunks of gathers in flight), then
 // all waves MFMA every staged chunk.  Returns n (ratings of this entity).
-template <int KT, bool COMBINE = true, bool TRI = false, bool FP8 = false>
+// WT: weighted normal equations -- ``values`` is ext[], rows are rescaled
+// by ``scale`` in staging, and COMBINE adds the symmetric base matrix G0
+// ([K][K] fp32, lower triangle read) to the finished image.
+template <int KT, bool COMBINE = true, bool TRI = false, bool FP8 = false,
+          bool WT = false>
 DEV_INLINE int gramian_to_lds(char* smem,
                               const long long* __restrict__ indptr,
                               const int* __restrict__ indices,
                               const float* __restrict__ values,
                               const void* __restrict__ factors,
-                              long long row, float reg) {
+                              long long row, float reg,
+                              const float* __restrict__ scale = nullptr,
+                              const float* __restrict__ G0 = nullptr) {
     constexpr int K = Geo<KT>::K;
     constexpr int NCH = FP8 ? Geo<KT>::NCH_FP8 : Geo<KT>::NCH_BF16;
     constexpr int SB = (K + 16) * (FP8 ? Geo<KT>::TROW8 : Geo<KT>::TROW);
@@ -555,10 +655,10 @@ DEV_INLINE int gramian_to_lds(char* smem,
     const int nchunks = (n + 31) >> 5;
     for (int r0 = 0; r0 < nchunks; r0 += NCHU) {
         if (team < NCHU && r0 + team < nchunks)
-            stage_chunk_w<KT, FP8, TW * WAVE>(
+            stage_chunk_w<KT, FP8, TW * WAVE, WT>(
                 smem + team * SB, indices, values, factors,
                 p0 + (long long)(r0 + team) * 32, n - (r0 + team) * 32,
-                tlane);
+                tlane, scale);
         __syncthreads();
         const int ns = min(NCHU, nchunks - r0);
         for (int sc = 0; sc < ns; ++sc) {
@@ -593,6 +693,26 @@ DEV_INLINE int gramian_to_lds(char* smem,
         }
     }
     __syncthreads();
+    if constexpr (WT && COMBINE) {
+        // A += G0.  Element (r, c) reads G0[max][min]: the lower triangle
+        // only, and the diagonal tiles' upper halves stay symmetric.
+        if constexpr (TRI) {
+            const int lr = tid >> 4, lc = tid & 15;   // one tile per pass
+            int I = 0, J = 0;
+            for (int t = 0; t < Geo<KT>::NA; ++t) {
+                const int r = I * 16 + lr, c = J * 16 + lc;
+                A[t * Geo<KT>::TSZ + lr * Geo<KT>::LDT + lc] +=
+                    G0[max(r, c) * K + min(r, c)];
+                if (++J > I) { ++I; J = 0; }
+            }
+        } else {
+            for (int i = tid; i < K * K; i += 256) {
+                const int r = i / K, c = i % K;
+                A[r * (K + 1) + c] += G0[max(r, c) * K + min(r, c)];
+            }
+        }
+        __syncthreads();
+    }
     if (COMBINE && tid < K) {
         bhi[tid] += blo[tid];                       // combined b
         float* dp = TRI

@@ -244,6 +244,39 @@ public:
                     " elements, got ", t.numel());
     }
 
+    // CSR pattern without values (the weighted kernels take scale / ext
+    // instead); returns nrows
+    int64_t csr_pattern(const torch::Tensor& indptr,
+                        const torch::Tensor& indices) {
+        tensor(indptr, kI64, "indptr");
+        tensor(indices, kI32, "indices");
+        TORCH_CHECK(indptr.dim() == 1 && indptr.numel() >= 1, fn_,
+                    ": indptr must be 1-D with nrows + 1 elements");
+        TORCH_CHECK(indices.dim() == 1, fn_, ": indices must be 1-D");
+        return indptr.numel() - 1;
+    }
+
+    // weighted normal equations: scale / ext fp32, 1-D, one per stored
+    // entry; base contiguous fp32 [k][k]
+    void weights(const torch::Tensor& scale, const torch::Tensor& ext,
+                 const torch::Tensor& base, const torch::Tensor& indices,
+                 int k) {
+        const torch::Tensor* per_entry[2] = {&scale, &ext};
+        const char* names[2] = {"scale", "ext"};
+        for (int i = 0; i < 2; ++i) {
+            tensor(*per_entry[i], kF32, names[i]);
+            TORCH_CHECK(per_entry[i]->dim() == 1 &&
+                            per_entry[i]->numel() == indices.numel(),
+                        fn_, ": ", names[i], " must be 1-D with one element "
+                        "per stored entry (", indices.numel(), "), got ",
+                        per_entry[i]->sizes());
+        }
+        tensor(base, kF32, "base");
+        TORCH_CHECK(base.dim() == 2 && base.size(0) == k && base.size(1) == k,
+                    fn_, ": base must be [", k, "][", k, "], got ",
+                    base.sizes());
+    }
+
     // optional launch schedule: empty, or int32 of length nrows
     const int* row_order(const torch::Tensor& t, int64_t nrows,
                          const char* name = "row_order") {
@@ -378,6 +411,111 @@ void als_solve_wavefused_db(torch::Tensor indptr, torch::Tensor indices,
                   factors.data_ptr(), f32(out_f32), lp.bf16p, lp.fp8p, order,
                   nrows, (float)reg, (int)variant, a.stream(stream)),
               a.name());
+}
+
+// ---- weighted normal equations (implicit feedback): the twins of
+// gramian / als_solve_fused / als_solve_wavefused with (scale, ext, base)
+// in place of values (fma_api.h has the contract)
+
+void gramian_w(torch::Tensor indptr, torch::Tensor indices,
+               torch::Tensor scale, torch::Tensor ext, torch::Tensor base,
+               torch::Tensor factors, torch::Tensor A_out,
+               torch::Tensor b_out, torch::Tensor row_order, double reg,
+               int64_t stream) {
+    Args a("gramian_w");
+    const int64_t nrows = a.csr_pattern(indptr, indices);
+    const bool fp8 = factors.scalar_type() == kU8;
+    const int k = a.factors(factors, fp8, "factors");
+    a.weights(scale, ext, base, indices, k);
+    a.square_rows(A_out, "A_out", nrows, k);
+    a.rows(b_out, kF32, "b_out", nrows, k);
+    const int* order = a.row_order(row_order, nrows);
+    check_hip(fma_gramian_w(k, fp8, i64(indptr), i32(indices), f32(scale),
+                            f32(ext), f32(base), factors.data_ptr(),
+                            f32(A_out), f32(b_out), order, nrows, (float)reg,
+                            a.stream(stream)),
+              a.name());
+}
+
+void als_solve_fused_w(torch::Tensor indptr, torch::Tensor indices,
+                       torch::Tensor scale, torch::Tensor ext,
+                       torch::Tensor base, torch::Tensor factors,
+                       torch::Tensor out_f32, torch::Tensor out_bf16,
+                       torch::Tensor out_fp8, torch::Tensor row_order,
+                       double reg, int64_t stream) {
+    Args a("als_solve_fused_w");
+    const int64_t nrows = a.csr_pattern(indptr, indices);
+    const bool fp8 = factors.scalar_type() == kU8;
+    const int k = a.factors(factors, fp8, "factors");
+    a.weights(scale, ext, base, indices, k);
+    a.rows(out_f32, kF32, "out_f32", nrows, k);
+    const LowpOut lp(a, out_f32, out_bf16, "out_bf16", out_fp8, "out_fp8");
+    TORCH_CHECK(fp8 ? !lp.bf16p : !lp.fp8p, a.name(), ": ",
+                fp8 ? "out_bf16 must be empty with e4m3 factors"
+                    : "out_fp8 must be empty with bf16 factors");
+    const int* order = a.row_order(row_order, nrows);
+    check_hip(fma_als_solve_fused_w(
+                  k, fp8, i64(indptr), i32(indices), f32(scale), f32(ext),
+                  f32(base), factors.data_ptr(), f32(out_f32), lp.bf16p,
+                  lp.fp8p, order, nrows, (float)reg, a.stream(stream)),
+              a.name());
+}
+
+void als_solve_wavefused_w(torch::Tensor indptr, torch::Tensor indices,
+                           torch::Tensor scale, torch::Tensor ext,
+                           torch::Tensor base, torch::Tensor factors,
+                           torch::Tensor out_f32, torch::Tensor out_bf16,
+                           torch::Tensor out_fp8, torch::Tensor row_order,
+                           double reg, int64_t stream) {
+    Args a("als_solve_wavefused_w");
+    const int64_t nrows = a.csr_pattern(indptr, indices);
+    const bool fp8 = factors.scalar_type() == kU8;
+    const int k = a.factors(factors, fp8, "factors");
+    TORCH_CHECK(k <= 64, a.name(), ": factors has rank ", k,
+                ", the wave-fused kernel handles at most 64");
+    a.weights(scale, ext, base, indices, k);
+    a.rows(out_f32, kF32, "out_f32", nrows, k);
+    const LowpOut lp(a, out_f32, out_bf16, "out_bf16", out_fp8, "out_fp8");
+    const int* order = a.row_order(row_order, nrows);
+    check_hip(fma_als_solve_wavefused_w(
+                  k, fp8, i64(indptr), i32(indices), f32(scale), f32(ext),
+                  f32(base), factors.data_ptr(), f32(out_f32), lp.bf16p,
+                  lp.fp8p, order, nrows, (float)reg, a.stream(stream)),
+              a.name());
+}
+
+// G [k][k] = F^T F of a bf16 / e4m3 table F [n][k], k = 16..128;
+// rows_per_part = 0 is the launcher's choice
+torch::Tensor factor_gram(torch::Tensor factors, int64_t rows_per_part,
+                          int64_t stream) {
+    Args a("factor_gram");
+    const bool fp8 = factors.scalar_type() == kU8;
+    const int k = a.factors(factors, fp8, "factors");
+    const int64_t n = factors.size(0);
+    TORCH_CHECK(n >= 1, a.name(), ": factors must have at least one row");
+    TORCH_CHECK(k <= 128, a.name(), ": factors has rank ", k,
+                ", need at most 128");
+    TORCH_CHECK(rows_per_part >= 0, a.name(),
+                ": rows_per_part must be >= 0 (0 = the launcher's choice)");
+    void* st = a.stream(stream);   // device check, before any allocation
+    const long long ws_bytes =
+        fma_factor_gram_workspace_bytes(n, k, rows_per_part);
+    TORCH_CHECK(ws_bytes >= 0, a.name(), ": bad shape");
+    auto opts = factors.options().dtype(kF32);
+    auto ws = torch::empty({ws_bytes / 4}, opts);
+    auto G = torch::empty({k, k}, opts);
+    check_hip(fma_factor_gram(k, fp8, factors.data_ptr(), n, rows_per_part,
+                              f32(G), ws.data_ptr(), ws_bytes, st),
+              a.name());
+    return G;
+}
+
+// Rows per part factor_gram uses for rows_per_part = 0; host-only.
+int64_t factor_gram_rows_per_part(int64_t n, int64_t k) {
+    const long long r = fma_factor_gram_rows_per_part(n, (int)k);
+    TORCH_CHECK(r > 0, "factor_gram_rows_per_part: need n >= 1 and k a "
+                       "multiple of 16 in 16..128");
+    return (int64_t)r;
 }
 
 // Batched solves A x = b from dense systems: A [n][k][k], b and x
@@ -700,6 +838,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("factors"), py::arg("out_f32"), py::arg("out_bf16"),
           py::arg("out_fp8"), py::arg("row_order"), py::arg("reg"),
           py::arg("stream"), py::arg("variant") = kBroadcastDefault);
+    m.def("gramian_w", &gramian_w);
+    m.def("als_solve_fused_w", &als_solve_fused_w);
+    m.def("als_solve_wavefused_w", &als_solve_wavefused_w);
+    m.def("factor_gram", &factor_gram, py::arg("factors"),
+          py::arg("rows_per_part"), py::arg("stream"));
+    m.def("factor_gram_rows_per_part", &factor_gram_rows_per_part);
     m.def("cholesky_solve", &cholesky_solve);
     m.def("cholesky_solve_ph", &cholesky_solve_ph);
     m.def("ldl_solve_wave", &ldl_solve_wave);

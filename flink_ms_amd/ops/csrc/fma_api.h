@@ -62,6 +62,50 @@ int fma_als_solve_wavefused_db(int k, const long long* indptr,
                                long long nrows, float reg, int variant,
                                void* stream);
 
+// ---- ALS, weighted normal equations (implicit feedback): als_kernels.hip
+// The twins of fma_gramian / fma_als_solve_fused / fma_als_solve_wavefused
+// with, per stored entry j, scale[j] and ext[j] (fp32, the length of
+// indices) in place of values, and the symmetric fp32 base matrix
+// base[k][k] (only its lower triangle is read):
+//   row~_j = round_D(scale[j] * dequant(factors[indices[j]]))
+//   A = base + sum_j row~_j row~_j^T + reg * n * I,  b = sum_j ext[j] row~_j
+// (ext through the same hi/lo pair as the explicit kernels' ratings).  All
+// three pointers are required.  The wave-fused twin has the default
+// broadcast level only.
+int fma_gramian_w(int k, int fp8, const long long* indptr, const int* indices,
+                  const float* scale, const float* ext, const float* base,
+                  const void* factors, float* A_out, float* b_out,
+                  const int* row_order, long long nrows, float reg,
+                  void* stream);
+int fma_als_solve_fused_w(int k, int fp8, const long long* indptr,
+                          const int* indices, const float* scale,
+                          const float* ext, const float* base,
+                          const void* factors, float* out_f32,
+                          unsigned short* out_bf16, unsigned char* out_fp8,
+                          const int* row_order, long long nrows, float reg,
+                          void* stream);
+int fma_als_solve_wavefused_w(int k, int fp8, const long long* indptr,
+                              const int* indices, const float* scale,
+                              const float* ext, const float* base,
+                              const void* factors, float* out_f32,
+                              unsigned short* out_bf16,
+                              unsigned char* out_fp8, const int* row_order,
+                              long long nrows, float reg, void* stream);
+
+// G [k][k] fp32 = sum over the n rows of the bf16 / e4m3 table factors
+// [n][k] of f f^T, full and exactly symmetric, k = 16..128.  Parts of
+// rows_per_part rows (0 = fma_factor_gram_rows_per_part; else rounded up to
+// a multiple of 32) are accumulated by one wave each into workspace
+// (fma_factor_gram_workspace_bytes, 4-byte aligned) and summed in part
+// order: bit-reproducible, no atomics.  The size helpers return -1 for a
+// bad shape (n < 1, k not a multiple of 16 in 16..128).
+int fma_factor_gram(int k, int fp8, const void* factors, long long n,
+                    long long rows_per_part, float* G, void* workspace,
+                    long long workspace_bytes, void* stream);
+long long fma_factor_gram_workspace_bytes(long long n, int k,
+                                          long long rows_per_part);
+long long fma_factor_gram_rows_per_part(long long n, int k);
+
 // ---- MFMA layout probes: fixed-size operands (als_kernels.hip)
 int fma_mfma_probe_f32(const float* A /*[16][4]*/, const float* B /*[4][16]*/,
                        float* D /*[16][16]*/, void* stream);

@@ -90,6 +90,232 @@ def als_solve_side_reference(
     return cholesky_solve_reference(A, b)
 
 
+# ------------------------------------------- weighted K1 + K2 (implicit ALS)
+#
+# Contract of the weighted kernels (docs/KERNELS.md "Implicit feedback"):
+# per stored entry j a scale s_j and an EXT value e_j, and one symmetric base
+# matrix G0 [k][k]:
+#   row~_j = round_D(s_j * F[indices[j]])        one fp32 multiply, RNE to D
+#   A = G0 + sum_j row~_j row~_j^T + reg * n * I
+#   b = sum_j pair_D(e_j) * row~_j               x = A^-1 b; n == 0 -> x = 0
+# ``gather`` names D: 'fp8' (e4m3), 'bf16', or None (fp32 tables: nothing is
+# rounded and pair_D is the identity).
+
+def _round_gather(t: torch.Tensor, gather: Optional[str]) -> torch.Tensor:
+    if gather == "fp8":
+        return t.to(torch.float8_e4m3fn).to(torch.float32)
+    if gather == "bf16":
+        return t.to(torch.bfloat16).to(torch.float32)
+    if gather is None:
+        return t
+    raise ValueError(f"gather must be 'fp8', 'bf16' or None, got {gather!r}")
+
+
+def rating_pair(r: torch.Tensor, gather: Optional[str]) -> torch.Tensor:
+    """pair_D: the hi/lo EXT-column representation of ``r`` in the gather
+    dtype, dequantized (hi = round_D(r), lo = round_D(r - hi))."""
+    r = r.to(torch.float32)
+    if gather is None:
+        return r
+    hi = _round_gather(r, gather)
+    return hi + _round_gather(r - hi, gather)
+
+
+def gather_of(factors: torch.Tensor) -> Optional[str]:
+    """The gather dtype a factor table selects: uint8 = e4m3 bytes, bf16,
+    anything else = unrounded fp32."""
+    if factors.dtype == torch.uint8:
+        return "fp8"
+    if factors.dtype == torch.bfloat16:
+        return "bf16"
+    return None
+
+
+def _table_f32(factors: torch.Tensor) -> torch.Tensor:
+    if factors.dtype == torch.uint8:
+        return factors.view(torch.float8_e4m3fn).to(torch.float32)
+    return factors.to(torch.float32)
+
+
+def effective_rows(csr: CSR, factors: torch.Tensor, scale: torch.Tensor,
+                   ext: torch.Tensor, gather="auto",
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(row~ [nnz, k], pair_D(ext) [nnz]) in fp32: exactly the operands the
+    weighted kernels feed their MFMAs, one row per stored entry."""
+    if gather == "auto":
+        gather = gather_of(factors)
+    q = _table_f32(factors)[csr.indices.long()]
+    rows = _round_gather(scale.to(torch.float32).unsqueeze(1) * q, gather)
+    return rows, rating_pair(ext, gather)
+
+
+def _weighted_systems(csr, factors, reg, scale, ext, base, gather, dtype,
+                      chunk=8192):
+    if gather == "auto":
+        gather = gather_of(factors)
+    k = factors.shape[1]
+    n_rows = csr.num_rows
+    dev = factors.device
+    counts = csr.row_counts()
+    A = base.to(dtype).unsqueeze(0).repeat(n_rows, 1, 1)
+    b = torch.zeros(n_rows, k, dtype=dtype, device=dev)
+    row_ids = torch.repeat_interleave(
+        torch.arange(n_rows, dtype=torch.int64, device=dev), counts)
+    f32 = _table_f32(factors)
+    for s in range(0, csr.nnz, chunk):
+        e = min(s + chunk, csr.nnz)
+        q = _round_gather(
+            scale[s:e].to(torch.float32).unsqueeze(1)
+            * f32[csr.indices[s:e].long()], gather).to(dtype)
+        r = rating_pair(ext[s:e], gather).to(dtype)
+        rid = row_ids[s:e]
+        A.index_add_(0, rid, q.unsqueeze(2) * q.unsqueeze(1))
+        b.index_add_(0, rid, q * r.unsqueeze(1))
+    diag = torch.arange(k, device=dev)
+    A[:, diag, diag] += reg * counts.to(dtype).unsqueeze(1)
+    return A, b, counts
+
+
+def gramian_weighted_reference(csr: CSR, factors: torch.Tensor, reg: float,
+                               scale: torch.Tensor, ext: torch.Tensor,
+                               base: torch.Tensor, gather="auto",
+                               ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Weighted normal equations in fp32: (A [rows, k, k], b [rows, k])."""
+    A, b, _ = _weighted_systems(csr, factors, reg, scale, ext, base, gather,
+                                torch.float32)
+    return A, b
+
+
+def gramian_weighted_f64(csr: CSR, factors: torch.Tensor, reg: float,
+                         scale: torch.Tensor, ext: torch.Tensor,
+                         base: torch.Tensor, gather="auto",
+                         ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Float64 oracle of the weighted normal equations on the exact
+    effective rows (row~ and pair_D(ext) are formed in fp32, as the contract
+    says, and are exact in float64; everything after is float64)."""
+    A, b, _ = _weighted_systems(csr, factors, reg, scale, ext, base, gather,
+                                torch.float64)
+    return A, b
+
+
+def _solve_nonempty(A, b, counts):
+    k = A.shape[-1]
+    empty = counts == 0
+    A = A.clone()
+    A[empty] = torch.eye(k, dtype=A.dtype, device=A.device)
+    x = torch.linalg.solve(A, b.unsqueeze(2)).squeeze(2)
+    x[empty] = 0
+    return x
+
+
+def als_solve_weighted_reference(csr: CSR, factors: torch.Tensor, reg: float,
+                                 scale: torch.Tensor, ext: torch.Tensor,
+                                 base: torch.Tensor, gather="auto",
+                                 ) -> torch.Tensor:
+    """One weighted ALS half-iteration in fp32 (Cholesky); rows without
+    stored entries come back as zeros."""
+    A, b, counts = _weighted_systems(csr, factors, reg, scale, ext, base,
+                                     gather, torch.float32)
+    k = A.shape[-1]
+    empty = counts == 0
+    A[empty] = torch.eye(k, dtype=A.dtype, device=A.device)
+    L = torch.linalg.cholesky(A)
+    x = torch.cholesky_solve(b.unsqueeze(2), L).squeeze(2)
+    x[empty] = 0
+    return x
+
+
+def als_solve_weighted_f64(csr: CSR, factors: torch.Tensor, reg: float,
+                           scale: torch.Tensor, ext: torch.Tensor,
+                           base: torch.Tensor, gather="auto") -> torch.Tensor:
+    """Float64 oracle of the weighted solve on the exact effective rows."""
+    A, b, counts = _weighted_systems(csr, factors, reg, scale, ext, base,
+                                     gather, torch.float64)
+    return _solve_nonempty(A, b, counts)
+
+
+def factor_gram_reference(factors: torch.Tensor) -> torch.Tensor:
+    """G = F^T F in fp32 over every row of the table."""
+    f = _table_f32(factors)
+    return f.T @ f
+
+
+def factor_gram_f64(factors: torch.Tensor) -> torch.Tensor:
+    """Float64 oracle of the factor Gram matrix (table entries are exact)."""
+    f = _table_f32(factors).to(torch.float64)
+    return f.T @ f
+
+
+def implicit_weights_reference(values: torch.Tensor, alpha: float,
+                               ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(scale, ext) of confidence-weighted ALS, in fp32 (Spark semantics:
+    negative and zero stored values are legal):
+      w = alpha * |r|,  s = sqrt(w),  e = (1 + w) / s if r > 0 else 0,
+      w == 0 -> s = e = 0."""
+    r = values.to(torch.float32)
+    w = float(alpha) * r.abs()
+    s = torch.sqrt(w)
+    pos = (r > 0) & (w > 0)
+    e = torch.where(pos, (1.0 + w) / torch.where(pos, s, torch.ones_like(s)),
+                    torch.zeros_like(s))
+    return s, e
+
+
+def implicit_dense_f64(csr: CSR, Y: torch.Tensor, alpha: float,
+                       reg: float) -> torch.Tensor:
+    """Textbook dense Hu-Koren-Volinsky update, float64, for tiny problems:
+    for every row u of ``csr`` (rows x all columns of Y)
+      x_u = (Y^T C_u Y + reg * n_u * I)^-1 Y^T C_u p_u,
+    c = 1 + alpha * |r| on stored entries and 1 elsewhere, p = [r > 0],
+    n_u = stored entries of the row (rows without any give 0)."""
+    Y = Y.to(torch.float64)
+    m, k = Y.shape
+    indptr = csr.indptr.tolist()
+    out = torch.zeros(csr.num_rows, k, dtype=torch.float64)
+    eye = torch.eye(k, dtype=torch.float64)
+    for u in range(csr.num_rows):
+        s, e = indptr[u], indptr[u + 1]
+        if s == e:
+            continue
+        idx = csr.indices[s:e].long()        # one entry per (row, column)
+        r = csr.values[s:e].to(torch.float64)
+        c = torch.ones(m, dtype=torch.float64)
+        c[idx] = 1.0 + float(alpha) * r.abs()
+        p = torch.zeros(m, dtype=torch.float64)
+        p[idx] = (r > 0).to(torch.float64)
+        A = Y.T @ (c.unsqueeze(1) * Y) + reg * (e - s) * eye
+        out[u] = torch.linalg.solve(A, Y.T @ (c * p))
+    return out
+
+
+def implicit_objective(csr: CSR, X: torch.Tensor, Y: torch.Tensor,
+                       alpha: float, reg: float) -> float:
+    """Confidence-weighted objective over the FULL rows x columns grid, in
+    float64: sum c (p - x^T y)^2 + reg * (sum n_u |x_u|^2 + sum n_i |y_i|^2),
+    c = 1 + alpha |r| and p = [r > 0] on the stored entries of ``csr`` (rows
+    = X, columns = Y), c = 1 and p = 0 elsewhere; n = stored entries per row
+    / per column.  The unobserved part is sum((X^T X) * (Y^T Y)), so the cost
+    is O(nnz k + (rows + cols) k^2), not the grid's."""
+    X = X.to(torch.float64).cpu()
+    Y = Y.to(torch.float64).cpu()
+    counts = csr.row_counts().cpu()
+    rid = torch.repeat_interleave(torch.arange(csr.num_rows), counts)
+    cid = csr.indices.long().cpu()
+    r = csr.values.to(torch.float64).cpu()
+    pred = (X[rid] * Y[cid]).sum(dim=1)
+    w = float(alpha) * r.abs()
+    p = (r > 0).to(torch.float64)
+    # every grid cell at c = 1, p = 0, then the stored entries' correction
+    total = ((X.T @ X) * (Y.T @ Y)).sum()
+    total = total + ((1.0 + w) * (p - pred) ** 2 - pred ** 2).sum()
+    ccount = torch.zeros(Y.shape[0], dtype=torch.float64)
+    ccount.index_add_(0, cid, torch.ones_like(r))
+    total = total + reg * ((counts.to(torch.float64)
+                            * (X * X).sum(dim=1)[: csr.num_rows]).sum()
+                           + (ccount * (Y * Y).sum(dim=1)).sum())
+    return float(total)
+
+
 # ---------------------------------------------------------------------- K3
 
 def sdca_epoch_reference(
