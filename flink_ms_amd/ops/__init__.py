@@ -588,6 +588,162 @@ def topk_chunk_items(nq: int, nc: int, topk: int) -> int:
     return int(_require_hip().topk_chunk_items(int(nq), int(nc), int(topk)))
 
 
+def _rank_args(nq: int, nv: int, q_idx, cand, exclude):
+    """Validate and normalise the index arguments of the rank-count entry
+    points.  Returns (q_idx, cand, exclude) as contiguous int64, the
+    exclusion slices reduced to candidate rows."""
+    q_idx = q_idx.long().contiguous()
+    if q_idx.dim() != 1:
+        raise ValueError("q_idx must be 1-D")
+    if q_idx.numel() and (int(q_idx.min()) < 0 or int(q_idx.max()) >= nq):
+        raise ValueError(f"q_idx entries must be rows of Q (0..{nq - 1})")
+    if cand is not None:
+        cand = cand.long().contiguous()
+        if cand.dim() != 1 or cand.numel() == 0:
+            raise ValueError("cand must be 1-D and non-empty")
+        if int(cand.min()) < 0 or int(cand.max()) >= nv:
+            raise ValueError(f"cand entries must be rows of V (0..{nv - 1})")
+        if torch.unique(cand).numel() != cand.numel():
+            raise ValueError("cand must not repeat a row")
+    if exclude is not None:
+        ptr, ex = exclude
+        ptr = ptr.long().contiguous()
+        ex = ex.long().contiguous()
+        if ptr.dim() != 1 or ptr.numel() != nq + 1 or ex.dim() != 1:
+            raise ValueError("exclude must be (excl_ptr [nq + 1], excl_rows)")
+        if (int(ptr[0]) < 0 or int(ptr[-1]) > ex.numel()
+                or bool((ptr[1:] < ptr[:-1]).any())):
+            raise ValueError("excl_ptr must be non-decreasing offsets into "
+                             "excl_rows")
+        ex = ex[int(ptr[0]):int(ptr[-1])]
+        ptr = ptr - ptr[0]
+        if ex.numel():
+            if int(ex.min()) < 0 or int(ex.max()) >= nv:
+                raise ValueError(
+                    f"excl_rows entries must be rows of V (0..{nv - 1})")
+            # strictly ascending inside every slice: a step down or a repeat
+            # is only allowed where the next slice starts
+            rising = torch.ones(ex.numel(), dtype=torch.bool,
+                                device=ex.device)
+            rising[1:] = ex[1:] > ex[:-1]
+            starts = ptr[:-1][ptr[:-1] < ex.numel()]
+            rising[starts] = True
+            if not bool(rising.all()):
+                raise ValueError("every exclusion slice must be strictly "
+                                 "ascending")
+            if cand is not None:
+                # excluded rows that are no candidates were never counted
+                is_cand = torch.zeros(nv, dtype=torch.bool, device=ex.device)
+                is_cand[cand.to(ex.device)] = True
+                keep = is_cand[ex]
+                kept = torch.zeros(ex.numel() + 1, dtype=torch.int64,
+                                   device=ex.device)
+                kept[1:] = torch.cumsum(keep, 0)
+                ptr = kept[ptr]
+                ex = ex[keep]
+        exclude = (ptr.contiguous(), ex.contiguous())
+    return q_idx, cand, exclude
+
+
+def rank_counts_vectors(Q: torch.Tensor, V: torch.Tensor, T: torch.Tensor,
+                        q_idx: torch.Tensor, skip: torch.Tensor,
+                        cand: Optional[torch.Tensor] = None,
+                        exclude: Optional[Tuple[torch.Tensor,
+                                                torch.Tensor]] = None,
+                        chunk_items: Optional[int] = None
+                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """:func:`rank_counts` with the targets given as VECTORS ``T`` [P, k]
+    plus ``skip`` [P], the row of V not to count (-1 = none), instead of as
+    rows of V: the form the serving store needs, where a target may live in
+    another factor table than the one being scanned."""
+    if (Q.dim() != 2 or V.dim() != 2 or T.dim() != 2
+            or Q.shape[1] != V.shape[1] or Q.shape[1] != T.shape[1]):
+        raise ValueError("Q, V and T must be 2-D with one rank")
+    nq, nv = Q.shape[0], V.shape[0]
+    q_idx, cand, exclude = _rank_args(nq, nv, q_idx, cand, exclude)
+    skip = skip.long().contiguous()
+    P = q_idx.numel()
+    if T.shape[0] != P or skip.dim() != 1 or skip.numel() != P:
+        raise ValueError("T and skip must hold one entry per pair")
+    if P and (int(skip.min()) < -1 or int(skip.max()) >= nv):
+        raise ValueError(f"skip entries must be -1 or rows of V "
+                         f"(0..{nv - 1})")
+    dev = Q.device
+    if P == 0:
+        return (torch.zeros(0, dtype=torch.int64, device=dev),
+                torch.zeros(0, dtype=torch.int64, device=dev),
+                torch.zeros(0, dtype=torch.float32, device=dev))
+    if Q.is_cuda:
+        ops = _require_hip()
+        none = _empty(dev)
+        ptr, ex = exclude if exclude is not None else (none, none)
+        return tuple(ops.rank_counts(
+            Q.to(torch.bfloat16).contiguous(),
+            V.to(torch.bfloat16).contiguous(),
+            T.to(device=dev, dtype=torch.bfloat16).contiguous(),
+            q_idx.to(dev), skip.to(dev),
+            cand.to(dev) if cand is not None else none,
+            ptr.to(dev), ex.to(dev), int(chunk_items or 0), _stream()))
+    # CPU: the fp32 reference over V with the targets appended as extra
+    # rows that are no candidates
+    rows = (torch.arange(nv, dtype=torch.int64) if cand is None
+            else cand.cpu())
+    Vx = torch.cat([V.cpu().float(), T.cpu().float()])
+    return reference._rank_counts(Q, Vx, q_idx, nv + torch.arange(P), rows,
+                                  exclude, torch.float32, skip=skip)
+
+
+def rank_counts(Q: torch.Tensor, V: torch.Tensor, q_idx: torch.Tensor,
+                t_idx: torch.Tensor, cand: Optional[torch.Tensor] = None,
+                exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                chunk_items: Optional[int] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Where a target item ranks for a query, fused score + count on the
+    GPU (the [P, nv] score matrix is never materialized).  For pair ``p``,
+    query ``Q[q_idx[p]]`` and target row ``t = t_idx[p]`` of V:
+
+    ``score[p]``   ``dot(Q[q_idx[p]], V[t])`` accumulated in fp32;
+    ``greater[p]`` candidate rows ``r != t`` outside the query's exclusion
+                   slice that score strictly above the target;
+    ``equal[p]``   those that score equal to it.
+
+    Scores compare as in :func:`topk_scores` (NaN below every number and
+    equal to NaN, -0 equal to +0) and are the same bits; the row plays no
+    part, so every tie convention follows from the two counts.  ``cand``:
+    int64 rows of V without repeats (``None`` = all).  ``exclude =
+    (excl_ptr [nq + 1], excl_rows)`` is indexed by QUERY row, each slice
+    strictly ascending: a sorted, deduplicated training CSR as it stands.
+    The target never counts, candidate or not, excluded or not.
+    ``chunk_items`` overrides the launcher's split of the candidates
+    (tests; the result does not depend on it).
+
+    Returns (greater int64 [P], equal int64 [P], score fp32 [P])."""
+    if Q.dim() != 2 or V.dim() != 2 or Q.shape[1] != V.shape[1]:
+        raise ValueError("Q and V must be 2-D with one rank")
+    nv = V.shape[0]
+    t_idx = t_idx.long().contiguous()
+    if t_idx.dim() != 1 or t_idx.numel() != q_idx.numel():
+        raise ValueError("q_idx and t_idx must be 1-D of one length")
+    if t_idx.numel() and (int(t_idx.min()) < 0 or int(t_idx.max()) >= nv):
+        raise ValueError(f"t_idx entries must be rows of V (0..{nv - 1})")
+    if Q.is_cuda:
+        t_dev = t_idx.to(V.device)
+        return rank_counts_vectors(Q, V, V[t_dev], q_idx, t_dev, cand,
+                                   exclude, chunk_items)
+    q_idx, cand, exclude = _rank_args(Q.shape[0], nv, q_idx, cand, exclude)
+    return reference.rank_counts_reference(Q, V, q_idx, t_idx, cand, exclude)
+
+
+def rank_chunk_items(P: int, nc: int) -> int:
+    """Candidates per chunk that a GPU ``rank_counts`` over ``P`` pairs and
+    ``nc`` candidates uses when ``chunk_items`` is not given: one wave
+    scans one (16-pair tile, chunk)."""
+    chunk = int(_require_hip().rank_chunk_items(int(P), int(nc)))
+    if chunk < 0:
+        raise ValueError("need P, nc >= 1 and nc < 2^31")
+    return chunk
+
+
 def sgd_update(U: torch.Tensor, V: torch.Tensor, u_idx: torch.Tensor,
                i_idx: torch.Tensor, r: torch.Tensor, lr: float,
                user_reg: float, item_reg: float) -> torch.Tensor:

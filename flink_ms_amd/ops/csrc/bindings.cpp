@@ -737,6 +737,94 @@ int64_t topk_chunk_items(int64_t nq, int64_t nc, int64_t topk) {
     return (int64_t)fma_topk_chunk_items(nq, nc, (int)topk);
 }
 
+// Rank counts: for pair p the query Q[q_idx[p]] (Q bf16 [nq][k]) against the
+// cand rows (empty = all) of V bf16 [nv][k], relative to the target VECTOR
+// T[p] (T bf16 [P][k]); skip [P] is the row of V not to count (-1 = none);
+// excl_ptr [nq+1] / excl_rows (both empty = none) are per-QUERY-ROW slices.
+// Returns (greater int64 [P], equal int64 [P], score fp32 [P]).  The
+// CONTENTS of q_idx, cand, excl_ptr and excl_rows index device memory and
+// are checked by the Python wrapper (ops.rank_counts); this binding checks
+// metadata.
+py::tuple rank_counts(torch::Tensor Q, torch::Tensor V, torch::Tensor T,
+                      torch::Tensor q_idx, torch::Tensor skip,
+                      torch::Tensor cand, torch::Tensor excl_ptr,
+                      torch::Tensor excl_rows, int64_t chunk_items,
+                      int64_t stream) {
+    Args a("rank_counts");
+    a.tensor(Q, kBF16, "Q");
+    a.tensor(V, kBF16, "V");
+    a.tensor(T, kBF16, "T");
+    TORCH_CHECK(Q.dim() == 2 && V.dim() == 2 && T.dim() == 2, a.name(),
+                ": Q, V and T must be 2-D");
+    TORCH_CHECK(Q.size(1) == V.size(1) && Q.size(1) == T.size(1), a.name(),
+                ": Q/V/T rank mismatch");
+    const int64_t nq = Q.size(0), nv = V.size(0), k = Q.size(1);
+    const int64_t np = T.size(0);
+    TORCH_CHECK(nq >= 1 && nv >= 1 && np >= 1, a.name(),
+                ": Q, V and T must have at least one row");
+    TORCH_CHECK(k >= 1 && k <= 128, a.name(), ": rank k = ", k,
+                " must be in 1..128");
+    TORCH_CHECK(chunk_items >= 0, a.name(),
+                ": chunk_items must be >= 0 (0 = the launcher's choice)");
+    a.tensor(q_idx, kI64, "q_idx");
+    a.tensor(skip, kI64, "skip");
+    TORCH_CHECK(q_idx.dim() == 1 && q_idx.numel() == np, a.name(),
+                ": q_idx must be 1-D with P = ", np, " elements, got ",
+                q_idx.numel());
+    TORCH_CHECK(skip.dim() == 1 && skip.numel() == np, a.name(),
+                ": skip must be 1-D with P = ", np, " elements, got ",
+                skip.numel());
+    const long long* candp = nullptr;
+    int64_t nc = nv;
+    if (a.optional(cand, kI64, "cand", 1)) {
+        TORCH_CHECK(cand.dim() == 1, a.name(), ": cand must be 1-D");
+        candp = i64(cand);
+        nc = cand.numel();
+    }
+    TORCH_CHECK(nv < (int64_t(1) << 31) && nc < (int64_t(1) << 31), a.name(),
+                ": V and cand must have fewer than 2^31 rows");
+    const long long* eptr = nullptr;
+    const long long* erows = nullptr;
+    if (a.optional(excl_ptr, kI64, "excl_ptr", 1)) {
+        TORCH_CHECK(excl_ptr.dim() == 1 && excl_ptr.numel() == nq + 1,
+                    a.name(), ": excl_ptr must be 1-D with nq + 1 = ", nq + 1,
+                    " elements, got ", excl_ptr.numel());
+        // an all-empty exclusion is no exclusion: the launcher never gets an
+        // excl_ptr without rows behind it
+        if (a.optional(excl_rows, kI64, "excl_rows", 1)) {
+            TORCH_CHECK(excl_rows.dim() == 1, a.name(),
+                        ": excl_rows must be 1-D");
+            eptr = i64(excl_ptr);
+            erows = i64(excl_rows);
+        }
+    } else {
+        TORCH_CHECK(excl_rows.numel() == 0, a.name(),
+                    ": excl_rows given without excl_ptr");
+    }
+    void* st = a.stream(stream);   // device check, before any allocation
+    const long long ws_bytes = fma_rank_workspace_bytes(np, nc, chunk_items);
+    TORCH_CHECK(ws_bytes >= 0, a.name(), ": bad shape");
+    auto opts = Q.options();
+    auto ws = torch::empty({(ws_bytes + 7) / 8}, opts.dtype(kI64));
+    auto greater = torch::empty({np}, opts.dtype(kI64));
+    auto equal = torch::empty({np}, opts.dtype(kI64));
+    auto score = torch::empty({np}, opts.dtype(kF32));
+    check_hip(fma_rank_counts(bf16(Q), bf16(V), bf16(T), i64(q_idx),
+                              i64(skip), candp, eptr, erows,
+                              (long long*)greater.data_ptr(),
+                              (long long*)equal.data_ptr(), f32(score),
+                              ws.data_ptr(), ws_bytes, np, nq, nv, nc, (int)k,
+                              chunk_items, st),
+              a.name());
+    return py::make_tuple(greater, equal, score);
+}
+
+// Chunk length rank_counts uses for chunk_items = 0, -1 for a bad shape
+// (P or nc < 1, nc >= 2^31); host-only.
+int64_t rank_chunk_items(int64_t np, int64_t nc) {
+    return (int64_t)fma_rank_chunk_items(np, nc);
+}
+
 // ------------------------------------------------- MFMA probes and dumps
 
 void mfma_probe_f32(torch::Tensor A, torch::Tensor B, torch::Tensor D,
@@ -859,6 +947,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("cand"), py::arg("excl_ptr"), py::arg("excl_rows"),
           py::arg("topk"), py::arg("chunk_items"), py::arg("stream"));
     m.def("topk_chunk_items", &topk_chunk_items);
+    m.def("rank_counts", &rank_counts, py::arg("Q"), py::arg("V"),
+          py::arg("T"), py::arg("q_idx"), py::arg("skip"), py::arg("cand"),
+          py::arg("excl_ptr"), py::arg("excl_rows"), py::arg("chunk_items"),
+          py::arg("stream"));
+    m.def("rank_chunk_items", &rank_chunk_items);
     m.def("dbg_stage_dump", &dbg_stage_dump);
     m.def("dbg_frag_dump", &dbg_frag_dump);
     m.def("dbg_gramian", &dbg_gramian);

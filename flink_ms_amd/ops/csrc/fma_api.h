@@ -173,6 +173,39 @@ long long fma_topk_workspace_bytes(long long nq, long long nc, int topk,
                                    long long chunk_items);
 long long fma_topk_chunk_items(long long nq, long long nc, int topk);
 
+// ---- rank counts: topk_kernels.hip
+// For each of the np pairs p, with query row Q[q_idx[p]] (Q bf16 [nq][k])
+// and target VECTOR T[p] (T bf16 [np][k]): score[p] = their fp32 dot, and
+// greater[p] / equal[p] = how many of the nc candidate rows of V [nv][k]
+// (cand, or null = rows 0..nv-1, then nc == nv) score strictly above /
+// equal to it, compared on the score word of the top-N key (NaN below -inf,
+// -0 == +0; the row plays no part).  Not counted: the row skip[p] of V (-1
+// = none; the target's own row when it lives in V) and the rows of the
+// exclusion slice excl_rows[excl_ptr[q_idx[p]] .. excl_ptr[q_idx[p] + 1])
+// (excl_ptr [nq+1], indexed by QUERY row; both null = no exclusions).
+// Scores are the same 32 bits fma_topk_scores computes for (query, row).
+// chunk_items = 0 lets the launcher choose (fma_rank_chunk_items); the
+// result does not depend on it.  The launcher validates 1 <= k <= 128, np,
+// nq, nc >= 1, nv and nc < 2^31 and the workspace (fma_rank_workspace_bytes
+// = np * chunks * 16, 8-byte aligned).  The PYTHON WRAPPER (ops.rank_counts)
+// owns the contents: 0 <= q_idx < nq, 0 <= cand < nv without repeats, and
+// excl_ptr non-decreasing offsets into excl_rows whose slices hold each row
+// at most once, every one of them a candidate -- the exclusions are taken
+// back out of the full count, so an excluded non-candidate or a repeated row
+// would be subtracted without having been counted.  The two size helpers
+// return -1 for a bad shape.
+int fma_rank_counts(const unsigned short* Q, const unsigned short* V,
+                    const unsigned short* T, const long long* q_idx,
+                    const long long* skip, const long long* cand,
+                    const long long* excl_ptr, const long long* excl_rows,
+                    long long* greater, long long* equal, float* score,
+                    void* workspace, long long workspace_bytes, long long np,
+                    long long nq, long long nv, long long nc, int k,
+                    long long chunk_items, void* stream);
+long long fma_rank_workspace_bytes(long long np, long long nc,
+                                   long long chunk_items);
+long long fma_rank_chunk_items(long long np, long long nc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,8 @@
 // Top-N recommendation kernels for MI355X (gfx950): fused Q.V^T scoring and
 // per-query top-k selection.  No reference analog (ALSPredict.java only
 // does point dots); the [queries][items] score matrix never exists in HBM.
+// The rank-count kernels (K9, second half of this file) score with the same
+// fragments and MFMA steps and count instead of select.
 //
 //   k_topk_partial  one WAVE owns (16-query tile) x (one chunk of the
 //                   candidate list).  Q fragments stay in registers; per
@@ -396,5 +398,298 @@ extern "C" int fma_topk_scores(
     if (err != 0) return err;
     k_topk_merge<<<dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st>>>(
         ws, out_scores, out_rows, nq, nchunks, topk);
+    return hipGetLastError();
+}
+
+// ================================================================ K9
+// Rank counts: for each (query, target) pair how many candidate rows score
+// strictly above / equal to the target, on the high word of topk_key (the
+// row plays no part: the tie-break is the caller's).  No reference analog.
+//
+//   k_rank_scan    one WAVE owns (16-pair tile) x (one candidate chunk).
+//                  A fragments are Q[q_idx[p0 + (lane & 15)]]; the B
+//                  fragments, topk_load_frag calls and MFMA step order are
+//                  those of k_topk_partial, so a (query, row) score is the
+//                  same 32 bits in both kernels.  A prelude runs the same
+//                  steps against the tile's own 16 target vectors: pair i's
+//                  target score is the diagonal element.  The scan keeps
+//                  4 x 2 integer counters per lane -- no LDS, no lists, no
+//                  exclusion search -- and writes one (greater, equal)
+//                  partial per (pair, chunk).
+//   k_rank_finish  one wave per pair sums the chunk partials and takes the
+//                  pair's exclusion slice back out: it scores the excluded
+//                  rows in 16-row tiles and subtracts those the scan counted.
+//                  Subtraction is only correct because the score bits here
+//                  are identical to the scan's: same fragments, same MFMA
+//                  steps, the query replicated into all 16 A rows (an MFMA
+//                  output element depends on its own A row and B column
+//                  only).  The launcher's contract makes every excluded row
+//                  a candidate, counted exactly once by the scan.
+//
+// All sums are integers: the result cannot depend on chunking or the grid.
+
+DEV_INLINE unsigned rank_word(float s) {
+    return (unsigned)(topk_key(s, 0u) >> 32);
+}
+
+DEV_INLINE long long rank_group_sum(unsigned x) {
+    // over the 16 lanes that share lane >> 4
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) x += __shfl_xor(x, off, WAVE);
+    return (long long)x;
+}
+
+template <int WPB>
+__launch_bounds__(WPB * 64)
+__global__ void k_rank_scan(const unsigned short* __restrict__ Q,
+                            const unsigned short* __restrict__ V,
+                            const unsigned short* __restrict__ T,
+                            const long long* __restrict__ q_idx,
+                            const long long* __restrict__ skip,
+                            const long long* __restrict__ cand,
+                            long long* __restrict__ ws,
+                            float* __restrict__ score, long long np,
+                            long long nq, long long nc, int k,
+                            long long chunk, long long nchunks,
+                            long long npt, int vec) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int g = lane >> 4, li = lane & 15;
+    const long long unit = (long long)blockIdx.x * WPB + wv;
+    if (unit >= npt * nchunks) return;     // waves are independent
+    const long long pt = unit % npt, ch = unit / npt;
+    const long long p0 = pt * 16;
+    const long long cstart = ch * chunk;
+    const long long cend = cstart + chunk < nc ? cstart + chunk : nc;
+    const int KS = (k + 31) >> 5;
+
+    // A fragments: Q[q_idx[p0 + li]][32 s + 8 g + 0..7], resident
+    bf16x8 qf[4];
+    {
+        const unsigned short* qrow = nullptr;
+        if (p0 + li < np) {
+            const long long qi = q_idx[p0 + li];
+            if (qi >= 0 && qi < nq) qrow = Q + qi * (long long)k;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            qf[s] = topk_load_frag(s < KS ? qrow : nullptr, k, 32 * s + 8 * g,
+                                   vec);
+    }
+
+    // prelude: the tile's 16 targets as B; lane li == 4 g + j holds pair
+    // 4 g + j's target score in acc[j]
+    unsigned tw[4];
+    long long sk[4];
+    {
+        const unsigned short* trow =
+            p0 + li < np ? T + (p0 + li) * (long long)k : nullptr;
+        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            if (s < KS)
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    qf[s],
+                    topk_load_frag(trow, k, 32 * s + 8 * g, vec), acc, 0, 0,
+                    0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long p = p0 + 4 * g + j;
+            if (ch == 0 && li == 4 * g + j && p < np) score[p] = acc[j];
+            tw[j] = rank_word(__shfl(acc[j], 20 * g + j, WAVE));
+            sk[j] = p < np ? skip[p] : -1;
+        }
+    }
+
+    unsigned gt[4] = {0u, 0u, 0u, 0u}, eq[4] = {0u, 0u, 0u, 0u};
+
+    auto load_tile = [&](long long base, long long& r, bf16x8 (&vf)[4]) {
+        const long long idx = base + li;
+        r = -1;
+        if (idx < cend) r = cand != nullptr ? cand[idx] : idx;
+        const unsigned short* vrow = r >= 0 ? V + r * (long long)k : nullptr;
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            vf[s] = topk_load_frag(s < KS ? vrow : nullptr, k,
+                                   32 * s + 8 * g, vec);
+    };
+
+    long long r_cur;
+    bf16x8 vf[4];
+    load_tile(cstart, r_cur, vf);
+    for (long long base = cstart; base < cend; base += 16) {
+        // the next tile's loads fly while this one is scored and counted
+        long long r_nxt = -1;
+        bf16x8 vn[4];
+        load_tile(base + 16, r_nxt, vn);
+
+        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            if (s < KS)
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[s], vf[s],
+                                                              acc, 0, 0, 0);
+        const bool live = r_cur >= 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned w = rank_word(acc[j]);
+            // a strict "greater" can never hit the target itself
+            gt[j] += (live && w > tw[j]) ? 1u : 0u;
+            eq[j] += (live && w == tw[j] && r_cur != sk[j]) ? 1u : 0u;
+        }
+        r_cur = r_nxt;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) vf[s] = vn[s];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long long p = p0 + 4 * g + j;
+        const long long sg = rank_group_sum(gt[j]);
+        const long long se = rank_group_sum(eq[j]);
+        if (li == 0 && p < np) {
+            long long* dst = ws + (p * nchunks + ch) * 2;
+            dst[0] = sg;
+            dst[1] = se;
+        }
+    }
+}
+
+__launch_bounds__(256)
+__global__ void k_rank_finish(const unsigned short* __restrict__ Q,
+                              const unsigned short* __restrict__ V,
+                              const long long* __restrict__ q_idx,
+                              const long long* __restrict__ skip,
+                              const long long* __restrict__ excl_ptr,
+                              const long long* __restrict__ excl_rows,
+                              const long long* __restrict__ ws,
+                              const float* __restrict__ score,
+                              long long* __restrict__ greater,
+                              long long* __restrict__ equal, long long np,
+                              long long nq, long long nv, int k,
+                              long long nchunks, int vec) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int g = lane >> 4, li = lane & 15;
+    const long long p = (long long)blockIdx.x * 4 + wv;
+    if (p >= np) return;
+    const int KS = (k + 31) >> 5;
+
+    long long sg = 0, se = 0;
+    for (long long c = lane; c < nchunks; c += 64) {
+        sg += ws[(p * nchunks + c) * 2];
+        se += ws[(p * nchunks + c) * 2 + 1];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sg += __shfl_xor(sg, off, WAVE);
+        se += __shfl_xor(se, off, WAVE);
+    }
+
+    const long long qi = q_idx[p];
+    const bool qok = qi >= 0 && qi < nq;
+    long long lo = 0, hi = 0;
+    if (excl_ptr != nullptr && qok) {
+        lo = excl_ptr[qi];
+        hi = excl_ptr[qi + 1];
+    }
+    if (lo < hi) {                         // wave-uniform
+        // the query in every A row: each lane's acc[0] is the score of the
+        // tile's row li, the same bits k_rank_scan compared
+        const unsigned short* qrow = Q + qi * (long long)k;
+        bf16x8 qf[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            qf[s] = topk_load_frag(s < KS ? qrow : nullptr, k, 32 * s + 8 * g,
+                                   vec);
+        const unsigned tw = rank_word(score[p]);
+        const long long sk = skip[p];
+        unsigned xg = 0u, xe = 0u;
+        for (long long base = lo; base < hi; base += 16) {
+            long long r = -1;
+            if (base + li < hi) r = excl_rows[base + li];
+            if (r >= nv) r = -1;           // never read past V
+            const unsigned short* vrow =
+                r >= 0 ? V + r * (long long)k : nullptr;
+            f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                if (s < KS)
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        qf[s],
+                        topk_load_frag(vrow, k, 32 * s + 8 * g, vec), acc, 0,
+                        0, 0);
+            const unsigned w = rank_word(acc[0]);
+            const bool counted = r >= 0 && r != sk;
+            xg += (counted && w > tw) ? 1u : 0u;
+            xe += (counted && w == tw) ? 1u : 0u;
+        }
+        // the four lane groups hold the same counts
+        sg -= rank_group_sum(xg);
+        se -= rank_group_sum(xe);
+    }
+    if (lane == 0) {
+        greater[p] = sg;
+        equal[p] = se;
+    }
+}
+
+static bool rank_shape_ok(long long np, long long nc, long long chunk_items) {
+    return np >= 1 && nc >= 1 && nc < (1ll << 31) && chunk_items >= 0;
+}
+
+// Chunk length the launcher picks: about 2048 (pair tile, chunk) waves over
+// the 256 CUs, chunks of at least 512 candidates, whole 16-item tiles.
+extern "C" long long fma_rank_chunk_items(long long np, long long nc) {
+    if (!rank_shape_ok(np, nc, 0)) return -1;
+    const long long npt = (np + 15) / 16;
+    long long want = 2048 / npt;
+    if (want < 1) want = 1;
+    long long chunk = (nc + want - 1) / want;
+    chunk = (chunk + 15) / 16 * 16;
+    return chunk < 512 ? 512 : chunk;
+}
+
+extern "C" long long fma_rank_workspace_bytes(long long np, long long nc,
+                                              long long chunk_items) {
+    if (!rank_shape_ok(np, nc, chunk_items)) return -1;
+    const long long chunk =
+        chunk_items > 0 ? chunk_items : fma_rank_chunk_items(np, nc);
+    const long long nchunks = (nc + chunk - 1) / chunk;
+    return np * nchunks * 2 * (long long)sizeof(long long);
+}
+
+extern "C" int fma_rank_counts(
+    const unsigned short* Q, const unsigned short* V, const unsigned short* T,
+    const long long* q_idx, const long long* skip, const long long* cand,
+    const long long* excl_ptr, const long long* excl_rows,
+    long long* greater, long long* equal, float* score, void* workspace,
+    long long workspace_bytes, long long np, long long nq, long long nv,
+    long long nc, int k, long long chunk_items, void* stream) {
+    if (!rank_shape_ok(np, nc, chunk_items) || k < 1 || k > 128 || nq < 1 ||
+        nv < 1 || nv >= (1ll << 31) || (cand == nullptr && nc != nv) ||
+        (excl_ptr != nullptr && excl_rows == nullptr))
+        return hipErrorInvalidValue;
+    const long long need = fma_rank_workspace_bytes(np, nc, chunk_items);
+    if (workspace == nullptr || workspace_bytes < need ||
+        ((size_t)workspace & 7u) != 0)
+        return hipErrorInvalidValue;
+    const long long chunk =
+        chunk_items > 0 ? chunk_items : fma_rank_chunk_items(np, nc);
+    const long long nchunks = (nc + chunk - 1) / chunk;
+    const long long npt = (np + 15) / 16;
+    if (npt * nchunks > (1ll << 31) || np > (1ll << 32))
+        return hipErrorInvalidValue;
+    const int vec = k % 8 == 0 && ((size_t)Q & 15u) == 0 &&
+                    ((size_t)V & 15u) == 0 && ((size_t)T & 15u) == 0;
+    hipStream_t st = (hipStream_t)stream;
+    constexpr int WPB = 4;
+    const long long units = npt * nchunks;
+    k_rank_scan<WPB><<<dim3((unsigned)((units + WPB - 1) / WPB)),
+                       dim3(WPB * 64), 0, st>>>(
+        Q, V, T, q_idx, skip, cand, (long long*)workspace, score, np, nq, nc,
+        k, chunk, nchunks, npt, vec);
+    int err = hipGetLastError();
+    if (err != 0) return err;
+    k_rank_finish<<<dim3((unsigned)((np + 3) / 4)), dim3(256), 0, st>>>(
+        Q, V, q_idx, skip, excl_ptr, excl_rows, (const long long*)workspace,
+        score, greater, equal, np, nq, nv, k, nchunks, vec);
     return hipGetLastError();
 }

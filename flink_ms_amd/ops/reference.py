@@ -571,3 +571,83 @@ def topk_scores_f64(
     """Float64 oracle of :func:`topk_scores_reference` (same contract,
     scores in float64; bf16/fp32 inputs are exact in it)."""
     return _topk_scores(Q, V, int(topk), cand, exclude, torch.float64)
+
+
+# ------------------------------------------------------------ rank counts
+
+def _rank_counts(Q, V, q_idx, t_idx, cand, exclude, dtype, skip=None):
+    # skip: the row not to count per pair (-1 = none) where that is not the
+    # target row itself (targets appended to V as rows that are no candidates)
+    Q, V = Q.cpu(), V.cpu()
+    q_idx, t_idx = q_idx.long().cpu(), t_idx.long().cpu()
+    skip = t_idx if skip is None else skip.long().cpu()
+    P, nv = q_idx.numel(), V.shape[0]
+    is_cand = torch.ones(nv, dtype=torch.bool)
+    if cand is not None:
+        is_cand = torch.zeros(nv, dtype=torch.bool)
+        is_cand[cand.long().cpu()] = True
+    if exclude is not None:
+        ptr, ex = (t.long().cpu() for t in exclude)
+    greater = torch.zeros(P, dtype=torch.int64)
+    equal = torch.zeros(P, dtype=torch.int64)
+    score = torch.zeros(P, dtype=dtype)
+    Vd = V.to(dtype)
+    step = max(1, (1 << 24) // nv)         # score blocks of <= 2^24 entries
+    for s in range(0, P, step):
+        qi, ti = q_idx[s:s + step], t_idx[s:s + step]
+        b = qi.numel()
+        # targets and candidates out of ONE product: equal vectors tie
+        S = Q[qi].to(dtype) @ Vd.T                              # [b, nv]
+        live = is_cand.expand(b, nv).clone()
+        if exclude is not None:
+            for j in range(b):
+                q = int(qi[j])
+                live[j, ex[int(ptr[q]):int(ptr[q + 1])]] = False
+        live[torch.arange(b), ti] = False                       # the target
+        sk = skip[s:s + b]
+        live[torch.arange(b)[sk >= 0], sk[sk >= 0]] = False
+        ts = S.gather(1, ti.unsqueeze(1))
+        # the order word of topk_key: NaN below -inf and equal to NaN;
+        # float comparison already has -0 == +0
+        nan, tnan = torch.isnan(S), torch.isnan(ts)
+        gt = ~nan & (tnan | (S > ts))
+        eq = (nan & tnan) | (S == ts)
+        greater[s:s + b] = (gt & live).sum(1)
+        equal[s:s + b] = (eq & live).sum(1)
+        score[s:s + b] = ts.squeeze(1)
+    return greater, equal, score
+
+
+def rank_counts_reference(
+    Q: torch.Tensor,
+    V: torch.Tensor,
+    q_idx: torch.Tensor,
+    t_idx: torch.Tensor,
+    cand: Optional[torch.Tensor] = None,
+    exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Where the target of each (query, target) pair ranks.  For pair ``p``
+    with query ``Q[q_idx[p]]`` and target row ``t = t_idx[p]`` of V:
+    ``score[p] = dot(Q[q_idx[p]], V[t])`` in fp32, and ``greater[p]`` /
+    ``equal[p]`` count the rows ``r != t`` of ``cand`` (``None`` = all rows
+    of V) outside ``excl_rows[excl_ptr[q]:excl_ptr[q+1]]``, ``q =
+    q_idx[p]`` (``exclude = (excl_ptr [nq + 1], excl_rows)``, indexed by
+    QUERY row), whose score is strictly above / equal to the target's.
+    Scores compare as in :func:`topk_scores_reference`: NaN below every
+    number and equal to NaN, -0 equal to +0; the row plays no part.  The
+    target never counts, candidate or not, excluded or not.  Returns
+    (greater int64 [P], equal int64 [P], score [P])."""
+    return _rank_counts(Q, V, q_idx, t_idx, cand, exclude, torch.float32)
+
+
+def rank_counts_f64(
+    Q: torch.Tensor,
+    V: torch.Tensor,
+    q_idx: torch.Tensor,
+    t_idx: torch.Tensor,
+    cand: Optional[torch.Tensor] = None,
+    exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Float64 oracle of :func:`rank_counts_reference` (same contract,
+    scores in float64; bf16/fp32 inputs are exact in it)."""
+    return _rank_counts(Q, V, q_idx, t_idx, cand, exclude, torch.float64)

@@ -11,6 +11,8 @@ server fronting the in-process stores:
   POST /model/{als|svm}/load        ingest from files on disk
   GET  /als/predict?user=&item=     ALSPredict semantics
   POST /als/recommend               top-n items per user (fused GPU top-k)
+  POST /als/rank                    where an item ranks for a user (fused
+                                    GPU score + rank count)
   POST /svm/predict                 SVMPredict / RangePartitionSVMPredict
   POST /sgd/update                  online SGD v1 step(s), SGD.java semantics
   POST /mse                         batch MSE over rating triples
@@ -63,6 +65,12 @@ class RecommendBody(BaseModel):
     users: List[str]
     n: int = 10
     exclude: Optional[List[List[str]]] = None   # item ids, one list per user
+
+
+class RankBody(BaseModel):
+    users: List[str]
+    items: List[str]                            # one (user, item) per position
+    exclude: Optional[List[List[str]]] = None   # item ids, one list per pair
 
 
 class SGDBody(BaseModel):
@@ -340,6 +348,30 @@ def create_app(als_store: Optional[ALSModelStore] = None,
         found, items, scores = als.recommend(
             [norm(u) for u in body.users], body.n, exclude)
         return {"found": found, "items": items, "scores": scores}
+
+    @app.post("/als/rank")
+    def als_rank(body: RankBody):
+        """Position of items[i] for users[i] among every live item of the
+        store (fused score + rank-count kernel; no reference analog):
+        ``greater`` / ``equal`` of the ``candidates`` other items score
+        above / the same, less the pair's ``exclude`` ids.  Ids are
+        normalised as in /als/recommend; an unknown user or item comes back
+        ``found`` False with zeros."""
+        if len(body.users) != len(body.items):
+            raise HTTPException(400, "users/items length mismatch")
+        if body.exclude is not None and len(body.exclude) != len(body.users):
+            raise HTTPException(400, "users/exclude length mismatch")
+
+        def norm(s: str) -> str:
+            return s.strip().upper()
+
+        exclude = (None if body.exclude is None else
+                   [[norm(i) for i in ids] for ids in body.exclude])
+        found, greater, equal, cands, score = als.rank(
+            [norm(u) for u in body.users], [norm(i) for i in body.items],
+            exclude)
+        return {"found": found, "greater": greater, "equal": equal,
+                "candidates": cands, "score": score}
 
     @app.post("/svm/predict")
     def svm_predict(body: SVMPredictBody):

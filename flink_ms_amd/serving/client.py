@@ -49,6 +49,18 @@ class QueryClientHelper:
         r.raise_for_status()
         return r.json()
 
+    def als_rank(self, users: List[str], items: List[str],
+                 exclude: Optional[List[List[str]]] = None) -> dict:
+        """Where ``items[i]`` ranks for ``users[i]`` (/als/rank):
+        ``{"found", "greater", "equal", "candidates", "score"}``, one entry
+        per pair; ``exclude[i]`` lists item ids that do not compete."""
+        payload: dict = {"users": users, "items": items}
+        if exclude is not None:
+            payload["exclude"] = exclude
+        r = self._client.post(f"{self.base}/als/rank", json=payload)
+        r.raise_for_status()
+        return r.json()
+
     def svm_predict(self, vector: str, output_decision_function: bool = False,
                     threshold_value: float = 0.0,
                     range_size: Optional[int] = None) -> dict:

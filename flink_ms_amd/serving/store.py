@@ -611,6 +611,113 @@ class ALSModelStore:
             scores[qi] = [float(sc) for sc, _ in best]
         return found, items, scores
 
+    def rank(self, user_ids: List[str], item_ids: List[str],
+             exclude: Optional[List[List[str]]] = None
+             ) -> Tuple[List[bool], List[int], List[int], List[int],
+                        List[float]]:
+        """Where item ``item_ids[i]`` ranks for user ``user_ids[i]`` among
+        every live item of the store, through the fused score + rank-count
+        kernel: at most one launch per item source, the counts summed.
+        ``exclude[i]`` lists item ids that do not compete in pair ``i``
+        (unknown ids are ignored).  Returns ``(found, greater, equal,
+        candidates, score)``: ``greater`` / ``equal`` live items other than
+        the target and outside the exclusion score strictly above / equal
+        to the target, out of ``candidates`` such items; the target sits at
+        one of the 0-based positions ``greater .. greater + equal``.  An
+        unknown user or item has ``found`` False and zeros."""
+        from .. import ops
+        if len(item_ids) != len(user_ids):
+            raise ValueError("users and items must pair up")
+        if exclude is not None and len(exclude) != len(user_ids):
+            raise ValueError("exclude must hold one list per pair")
+        with self._lock:
+            um, ua = self._batch_rows(user_ids, "U")
+            im, ia = self._batch_rows(item_ids, "I")
+            mirror = self._mirror
+            blocks = self._blocks
+            _, (m_cand, m_ids), (b_cand, b_ids) = self._item_candidates()
+            found_t = ((um >= 0) | (ua >= 0)) & ((im >= 0) | (ia >= 0))
+            sel = found_t.nonzero(as_tuple=True)[0].tolist()
+            # exclusion ids -> sorted live rows per source
+            ex_m: List[List[int]] = [[] for _ in sel]
+            ex_b: List[List[int]] = [[] for _ in sel]
+            if exclude is not None:
+                idmap = blocks.idmap["I"] if blocks is not None else {}
+                for j, qi in enumerate(sel):
+                    rm, rb = set(), set()
+                    for item in exclude[qi]:
+                        row = self._rows.get(als_state_key(item, "I"))
+                        if row is not None:
+                            rm.add(row)
+                            continue
+                        try:
+                            row = idmap.get(int(item))
+                        except ValueError:
+                            row = None
+                        if row is not None:
+                            rb.add(row)
+                    ex_m[j] = sorted(r for r in rm if r in m_ids)
+                    ex_b[j] = sorted(r for r in rb if r in b_ids)
+        n = len(user_ids)
+        found = found_t.tolist()
+        greater, equal, cands = [0] * n, [0] * n, [0] * n
+        scores = [0.0] * n
+        if not sel:
+            return found, greater, equal, cands, scores
+        dev = self.device
+        sel_t = torch.tensor(sel, dtype=torch.int64)
+
+        def gather(kind: str, mrow: torch.Tensor, arow: torch.Tensor):
+            # vectors on the device, mirror first
+            k = (mirror if mirror is not None else blocks.dev[kind]).shape[1]
+            out = torch.zeros(len(sel), k, dtype=torch.bfloat16, device=dev)
+            in_m = mrow >= 0
+            if bool(in_m.any()):
+                out[in_m.to(dev)] = mirror[mrow[in_m].to(dev)]
+            if bool((~in_m).any()):
+                out[(~in_m).to(dev)] = blocks.dev[kind][arow[~in_m].to(dev)]
+            return out
+
+        Q = gather("U", um[sel_t], ua[sel_t])
+        T = gather("I", im[sel_t], ia[sel_t])
+        every = torch.arange(len(sel), dtype=torch.int64, device=dev)
+        g_sum = torch.zeros(len(sel), dtype=torch.int64)
+        e_sum = torch.zeros(len(sel), dtype=torch.int64)
+        c_sum = [0] * len(sel)
+        s_dev = None
+        for V, cand, ids, ex, skip in (
+                (mirror, m_cand, m_ids, ex_m, im[sel_t]),
+                (blocks.dev["I"] if blocks is not None and "I" in blocks.dev
+                 else None, b_cand, b_ids, ex_b, ia[sel_t])):
+            if V is None or cand is None:
+                continue
+            excl = None
+            if exclude is not None:
+                ptr = [0]
+                for rows in ex:
+                    ptr.append(ptr[-1] + len(rows))
+                excl = (torch.tensor(ptr, dtype=torch.int64).to(dev),
+                        torch.tensor([r for rows in ex for r in rows],
+                                     dtype=torch.int64).to(dev))
+            g, e, sc = ops.rank_counts_vectors(Q, V, T, every, skip.to(dev),
+                                               cand=cand, exclude=excl)
+            if s_dev is None:
+                s_dev = sc         # the bits compared; one per source, equal
+            g_sum += g.cpu()
+            e_sum += e.cpu()
+            for j, s in enumerate(skip.tolist()):
+                own = s >= 0 and s in ids and s not in ex[j]
+                c_sum[j] += len(ids) - len(ex[j]) - int(own)
+        if s_dev is None:          # no live item at all: a plain K5 dot
+            s_dev = ops.predict_dot(Q, T, every, every)
+        s_all = s_dev.cpu().tolist()
+        for j, qi in enumerate(sel):
+            greater[qi] = int(g_sum[j])
+            equal[qi] = int(e_sum[j])
+            cands[qi] = c_sum[j]
+            scores[qi] = float(s_all[j])
+        return found, greater, equal, cands, scores
+
     # -------------------------------------------------------- online SGD
 
     def sgd_update(self, user_id: str, item_id: str, rating: float,
