@@ -18,7 +18,7 @@ def _rand_csr(rows, cols, nnz, seed, device):
     return csr_from_coo(r, c, v, rows, cols).to(device)
 
 
-@pytest.mark.parametrize("k", [16, 32, 64, 128])
+@pytest.mark.parametrize("k", [16, 32, 48, 64, 80, 96, 112, 128])
 def test_gramian_parity(gpu, k):
     csr = _rand_csr(rows=300, cols=200, nnz=20_000, seed=k, device=gpu)
     fac_bf16 = (torch.randn(200, k, generator=torch.Generator().manual_seed(2))
