@@ -1126,15 +1126,10 @@ __global__ void k_als_solve_wavefused(const long long* __restrict__ indptr,
         }
         return;
     }
-    {   // zero the EXT pad rows K+2..K+15 of my NCHW buffers (wave-local)
-        constexpr int SEGS = FP8 ? 8 : 16;
-        for (int i = lane; i < NCHW * 14 * SEGS; i += WAVE) {
-            const int b = i / (14 * SEGS), r2 = i % (14 * SEGS);
-            const int row = K + 2 + r2 / SEGS, seg = r2 % SEGS;
-            *(unsigned*)(buf + b * SB + (long long)row * TROW + seg * 4) =
-                0u;
-        }
-    }
+    // zero the EXT pad rows K+2..K+15 of my NCHW buffers (wave-local)
+#pragma unroll
+    for (int b = 0; b < NCHW; ++b)
+        stage_zero_pad<KT, FP8>(buf + b * SB, lane, WAVE);
     f32x4 T[NA], E[KT];
     if constexpr (WT) {
         wavefused_load_base<KT>(T, G0, g4, li);
@@ -1147,14 +1142,26 @@ __global__ void k_als_solve_wavefused(const long long* __restrict__ indptr,
     const int nchunks = (n + 31) >> 5;
     for (int ch = 0; ch < nchunks; ch += NCHW) {
         if constexpr (NCHW == 2) {
+            // Everything is counted from the pair's first rating, cb, with
+            // rem ratings left: both wave-uniform.  A full trip (all 64
+            // ratings present) is the common case and takes the unguarded
+            // staging, see stage_gather4.  When chunk ch+1 does not exist
+            // its rows all lie past rem and stage as zeros into the second
+            // buffer, which is then not read.
+            const int rem = n - ch * 32;
+            const bool full = rem >= 64;
+            const long long cb = p0 + (long long)ch * 32;
+            // the EXT rows have a lane map of their own: lanes 0-31 own
+            // the ratings of chunk ch, lanes 32-63 those of chunk ch+1,
+            // so lane l owns rating l of the pair
+            const float xr = stage_ext_load(values, cb, rem, lane, full);
             const int sub = (lane >= NT) ? 1 : 0;
-            const int lch = ch + sub;
-            if (lch < nchunks && lane < 2 * NT)
-                stage_chunk_w<KT, FP8, NT, WT>(buf + sub * SB, indices,
-                                               values, factors,
-                                               p0 + (long long)lch * 32,
-                                               n - lch * 32, lane - sub * NT,
-                                               scale);
+            if (2 * NT == WAVE || lane < 2 * NT)
+                stage_gather_w<KT, FP8, NT, WT>(buf + sub * SB, indices,
+                                                factors, cb, rem,
+                                                lane - sub * NT, 32 * sub,
+                                                full, scale);
+            stage_ext_commit<KT, FP8>(buf + (lane >> 5) * SB, lane & 31, xr);
         } else {
             stage_chunk_w<KT, FP8, WAVE, WT>(buf, indices, values, factors,
                                              p0 + (long long)ch * 32,

@@ -88,7 +88,10 @@ DEV_INLINE constexpr int lo_tile_i(int t) {
 // writes 8 ds_write_b64 transposed columns.  fp8: task (q, c16) loads
 // 4x16B row pieces (a whole k<=64 e4m3 row is ONE 16-B load x4 lanes) and
 // writes 16 ds_write_b32 transposed columns.  nrem = ratings left in the
-// entity (rows >= nrem zero-filled).
+// entity (rows >= nrem zero-filled).  The pieces: stage_gather4 (loads),
+// stage_gather_w (+ transpose and LDS writes), stage_ext_load /
+// stage_ext_commit (EXT rows, one rating per lane), stage_chunk_w (one
+// whole chunk), stage_zero_pad (pad rows).
 //
 // WT (weighted normal equations, docs/KERNELS.md "Implicit feedback"): each
 // gathered row is rescaled by its rating's scale[] entry between the gather
@@ -157,37 +160,109 @@ DEV_INLINE uint4 stage_rescale_piece(uint4 x, float s) {
                      stage_rescale_bf16x2(x.w, s)};
 }
 
+// An empty statement the optimizer can neither duplicate nor merge.
+#define STAGE_NO_SINK() asm volatile("")
+
+// One gather task's four row pieces: ratings row0..row0+3 counted from CSR
+// position ``base``, 16 bytes (WIDEN: 8) at byte offset ``coff`` of each
+// ROWB-byte factor row.  ``base`` and ``nrem`` (ratings left from base on)
+// are WAVE-UNIFORM; row0 is the lane's own.
+//
+// full -- wave-uniform too, and it promises that every rating any lane of
+// the wave asks for in this call is present: the task's four consecutive
+// indices (WT: and scales) arrive as ONE 16-byte load each, then the four
+// row loads issue back to back.  Two waits, no per-row branch, no zero
+// fill.  The CSR offset is arbitrary, so the wide loads are only 4-byte
+// aligned (memcpy spells that out).
+//
+// Otherwise every row is guarded as before: a row past the entity's range
+// is neither indexed nor loaded -- the last entity's range ends with the
+// allocation, so nothing wide may reach past it -- and stages as zeros.
+template <int ROWB, bool WT, bool IDENT, bool WIDEN>
+DEV_INLINE void stage_gather4(uint4 (&v)[4], float (&sc)[4],
+                              const int* __restrict__ indices,
+                              const char* __restrict__ factors,
+                              const float* __restrict__ scale,
+                              long long base, int nrem, int row0, int coff,
+                              bool full) {
+    if constexpr (!IDENT && !WIDEN) {
+        if (full) {
+            int idx[4];
+            __builtin_memcpy(idx, indices + base + (unsigned)row0, 16);
+            if constexpr (WT)
+                __builtin_memcpy(sc, scale + base + (unsigned)row0, 16);
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+                v[m] = *(const uint4*)(factors + (long long)idx[m] * ROWB
+                                       + coff);
+            // Ends the block with something the guarded path has no twin
+            // of: the optimizer otherwise sinks the last row's load out of
+            // both paths into one guarded block, behind a wait of its own.
+            STAGE_NO_SINK();
+            return;
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        uint4 x = {0, 0, 0, 0};
+        const int row = row0 + m;
+        if (row < nrem) {
+            long long col;
+            if constexpr (IDENT) col = base + row;
+            else col = indices[base + (unsigned)row];
+            if constexpr (WIDEN)
+                x = stage_widen_fp8x8(
+                    *(const uint2*)(factors + col * (long long)ROWB + coff));
+            else
+                x = *(const uint4*)(factors + col * (long long)ROWB + coff);
+            if constexpr (WT) sc[m] = scale[base + (unsigned)row];
+        }
+        v[m] = x;
+    }
+}
+
+// 4x4 byte transpose of one dword of four row pieces: out[c] holds byte c
+// of a0..a3 (a0 in the low byte).  Two-stage v_perm_b32 butterfly, 8
+// permutes for 4 words: stage one interleaves the bytes of (a0, a1) and of
+// (a2, a3), stage two gathers the halfwords.  v_perm_b32 selects bytes 0-3
+// from its SECOND source and 4-7 from its first.
+DEV_INLINE void stage_transpose4x4_b8(unsigned a0, unsigned a1, unsigned a2,
+                                      unsigned a3, unsigned* out) {
+    const unsigned p01l = __builtin_amdgcn_perm(a1, a0, 0x05010400u);
+    const unsigned p01h = __builtin_amdgcn_perm(a1, a0, 0x07030602u);
+    const unsigned p23l = __builtin_amdgcn_perm(a3, a2, 0x05010400u);
+    const unsigned p23h = __builtin_amdgcn_perm(a3, a2, 0x07030602u);
+    out[0] = __builtin_amdgcn_perm(p23l, p01l, 0x05040100u);
+    out[1] = __builtin_amdgcn_perm(p23l, p01l, 0x07060302u);
+    out[2] = __builtin_amdgcn_perm(p23h, p01h, 0x05040100u);
+    out[3] = __builtin_amdgcn_perm(p23h, p01h, 0x07060302u);
+}
+
+// The gather + transpose of one chunk (no EXT rows) by NLANES lanes
+// (``lane`` counts from 0 within them).  The chunk is ratings crow0 ..
+// crow0+31 counted from CSR position ``base``; base, nrem and full as in
+// stage_gather4, crow0 may differ between the lanes of a wave (split-wave
+// staging: one half per chunk).
 template <int KT, bool FP8, int NLANES = WAVE, bool WT = false,
           bool IDENT = false, bool WIDEN = false>
-DEV_INLINE void stage_chunk_w(char* buf,
-                              const int* __restrict__ indices,
-                              const float* __restrict__ values,
-                              const void* __restrict__ factors_v,
-                              long long base, int nrem, int lane,
-                              const float* __restrict__ scale = nullptr) {
+DEV_INLINE void stage_gather_w(char* buf,
+                               const int* __restrict__ indices,
+                               const void* __restrict__ factors_v,
+                               long long base, int nrem, int lane, int crow0,
+                               bool full,
+                               const float* __restrict__ scale = nullptr) {
     constexpr int K = Geo<KT>::K;
     constexpr int TROW = FP8 ? Geo<KT>::TROW8 : Geo<KT>::TROW;
+    const char* factors = (const char*)factors_v;
     if constexpr (FP8) {
-        const unsigned char* factors = (const unsigned char*)factors_v;
         constexpr int NT = 8 * (K / 16);
         for (int t = lane; t < NT; t += NLANES) {
             const int q = t & 7, c16 = t >> 3;
             uint4 v[4];
             [[maybe_unused]] float sc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                uint4 x = {0, 0, 0, 0};
-                const int row = 4 * q + m;
-                if (row < nrem) {
-                    long long col;
-                    if constexpr (IDENT) col = base + row;
-                    else col = indices[base + row];
-                    x = *(const uint4*)(factors + col * (long long)K
-                                        + c16 * 16);
-                    if constexpr (WT) sc[m] = scale[base + row];
-                }
-                v[m] = x;
-            }
+            stage_gather4<K, WT, IDENT, false>(v, sc, indices, factors, scale,
+                                               base, nrem, crow0 + 4 * q,
+                                               c16 * 16, full);
             if constexpr (WT) {
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
@@ -195,41 +270,24 @@ DEV_INLINE void stage_chunk_w(char* buf,
             }
             char* rb = buf + (long long)(16 * c16) * TROW + q * 4;
 #pragma unroll
-            for (int cc = 0; cc < 16; ++cc) {
-                unsigned wd = 0;
+            for (int d = 0; d < 4; ++d) {
+                unsigned wd[4];
+                stage_transpose4x4_b8((&v[0].x)[d], (&v[1].x)[d],
+                                      (&v[2].x)[d], (&v[3].x)[d], wd);
 #pragma unroll
-                for (int m = 0; m < 4; ++m)
-                    wd |= (((&v[m].x)[cc >> 2] >> (8 * (cc & 3))) & 0xffu)
-                          << (8 * m);
-                *(unsigned*)(rb + (long long)cc * TROW) = wd;
+                for (int c = 0; c < 4; ++c)
+                    *(unsigned*)(rb + (long long)(4 * d + c) * TROW) = wd[c];
             }
         }
     } else {
-        const unsigned short* factors = (const unsigned short*)factors_v;
         constexpr int NT = 8 * (K / 8);
         for (int t = lane; t < NT; t += NLANES) {
             const int q = t & 7, c8 = t >> 3;
             uint4 v[4];
             [[maybe_unused]] float sc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                uint4 x = {0, 0, 0, 0};
-                const int row = 4 * q + m;
-                if (row < nrem) {
-                    long long col;
-                    if constexpr (IDENT) col = base + row;
-                    else col = indices[base + row];
-                    if constexpr (WIDEN)
-                        x = stage_widen_fp8x8(*(const uint2*)(
-                            (const unsigned char*)factors_v
-                            + col * (long long)K + c8 * 8));
-                    else
-                        x = *(const uint4*)(factors + col * (long long)K
-                                            + c8 * 8);
-                    if constexpr (WT) sc[m] = scale[base + row];
-                }
-                v[m] = x;
-            }
+            stage_gather4<(WIDEN ? K : 2 * K), WT, IDENT, WIDEN>(
+                v, sc, indices, factors, scale, base, nrem, crow0 + 4 * q,
+                WIDEN ? c8 * 8 : c8 * 16, full);
             if constexpr (WT) {
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
@@ -252,54 +310,153 @@ DEV_INLINE void stage_chunk_w(char* buf,
             }
         }
     }
-    if constexpr (IDENT) return;
-    if (lane < 8) {  // rating hi/lo EXT rows K, K+1
-        if constexpr (FP8) {
-            unsigned h = 0, l = 0;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int row = 4 * lane + m;
-                const float r = (row < nrem) ? values[base + row] : 0.0f;
-                const unsigned char hb = f2fp8(r);
-                const unsigned char lb = f2fp8(r - fp82f(hb));
-                h |= ((unsigned)hb) << (8 * m);
-                l |= ((unsigned)lb) << (8 * m);
-            }
-            *(unsigned*)(buf + (long long)K * TROW + lane * 4) = h;
-            *(unsigned*)(buf + (long long)(K + 1) * TROW + lane * 4) = l;
-        } else {
-            unsigned h2[2] = {0, 0}, l2[2] = {0, 0};
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int row = 4 * lane + m;
-                const float r = (row < nrem) ? values[base + row] : 0.0f;
-                const unsigned short h = f2bf(r);
-                const unsigned short l = f2bf(r - bf2f(h));
-                h2[m >> 1] |= ((unsigned)h) << (16 * (m & 1));
-                l2[m >> 1] |= ((unsigned)l) << (16 * (m & 1));
-            }
-            *(uint2*)(buf + (long long)K * TROW + lane * 8) =
-                uint2{h2[0], h2[1]};
-            *(uint2*)(buf + (long long)(K + 1) * TROW + lane * 8) =
-                uint2{l2[0], l2[1]};
-        }
+}
+
+// The rating hi/lo EXT rows K, K+1, ONE RATING PER LANE: the lane that
+// owns rating r of the chunk loads it, converts it once and places its hi
+// and lo element (e4m3 byte / bf16 halfword) itself.  A wave-level
+// instruction costs the same with 8 live lanes as with 32, so the
+// conversion runs once per chunk instead of four times in series.
+//
+// The load comes first and the commit last in a staging call, so the value
+// arrives behind the gather's own waits.  ``row`` is the rating's position
+// counted from the wave-uniform ``base``; one past the entity's range
+// (row >= nrem) is not loaded and stages as 0; full as in stage_gather4.
+// WT passes ext[] as ``values``.
+DEV_INLINE float stage_ext_load(const float* __restrict__ values,
+                                long long base, int nrem, int row,
+                                bool full) {
+    float x = 0.0f;
+    if (full) {
+        x = values[base + (unsigned)row];
+        STAGE_NO_SINK();
+    } else if (row < nrem) {
+        x = values[base + (unsigned)row];
+    }
+    return x;
+}
+
+template <int KT, bool FP8>
+DEV_INLINE void stage_ext_commit(char* buf, int r, float x) {
+    constexpr int K = Geo<KT>::K;
+    constexpr int TROW = FP8 ? Geo<KT>::TROW8 : Geo<KT>::TROW;
+    if constexpr (FP8) {
+        const unsigned char hb = f2fp8(x);
+        const unsigned char lb = f2fp8(x - fp82f(hb));
+        *(unsigned char*)(buf + (long long)K * TROW + r) = hb;
+        *(unsigned char*)(buf + (long long)(K + 1) * TROW + r) = lb;
+    } else {
+        const unsigned short h = f2bf(x);
+        const unsigned short l = f2bf(x - bf2f(h));
+        *(unsigned short*)(buf + (long long)K * TROW + r * 2) = h;
+        *(unsigned short*)(buf + (long long)(K + 1) * TROW + r * 2) = l;
     }
 }
 
-// Zero the never-restaged EXT pad rows K+2..K+15 of all NCH stage buffers
-// once per entity (block-wide).
+// The EXT rows the earlier way: 8 lanes convert four ratings each and write
+// whole words.  Kept for the one instantiation (EXT8 below) that the
+// per-lane form pushes over a register-allocation cliff.
+template <int KT, bool FP8>
+DEV_INLINE void stage_ext_quad_w(char* buf, const float* __restrict__ values,
+                                 long long base, int nrem, int lane) {
+    constexpr int K = Geo<KT>::K;
+    constexpr int TROW = FP8 ? Geo<KT>::TROW8 : Geo<KT>::TROW;
+    if constexpr (FP8) {
+        unsigned h = 0, l = 0;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int row = 4 * lane + m;
+            const float r = (row < nrem) ? values[base + row] : 0.0f;
+            const unsigned char hb = f2fp8(r);
+            const unsigned char lb = f2fp8(r - fp82f(hb));
+            h |= ((unsigned)hb) << (8 * m);
+            l |= ((unsigned)lb) << (8 * m);
+        }
+        *(unsigned*)(buf + (long long)K * TROW + lane * 4) = h;
+        *(unsigned*)(buf + (long long)(K + 1) * TROW + lane * 4) = l;
+    } else {
+        unsigned h2[2] = {0, 0}, l2[2] = {0, 0};
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int row = 4 * lane + m;
+            const float r = (row < nrem) ? values[base + row] : 0.0f;
+            const unsigned short h = f2bf(r);
+            const unsigned short l = f2bf(r - bf2f(h));
+            h2[m >> 1] |= ((unsigned)h) << (16 * (m & 1));
+            l2[m >> 1] |= ((unsigned)l) << (16 * (m & 1));
+        }
+        *(uint2*)(buf + (long long)K * TROW + lane * 8) = uint2{h2[0], h2[1]};
+        *(uint2*)(buf + (long long)(K + 1) * TROW + lane * 8) =
+            uint2{l2[0], l2[1]};
+    }
+}
+
+// Gather + EXT rows of one chunk (ratings base.. of the CSR, nrem left) by
+// NLANES >= 32 lanes (``lane`` counts from 0 within them); nrem must be
+// uniform over those lanes' waves.  WIDE: take the unguarded path on a
+// full chunk and load the rating ahead of the gather.  It holds four
+// indices, four row pieces and the rating at once, which cost the block
+// kernels and the single-chunk bf16 wave-fused kernel registers they do
+// not have (a wave of occupancy at k = 112 / 128, a spill at k = 64), so
+// those keep the guarded gather and stage the rating before it.
+// EXT8: the 8-lane EXT conversion (stage_ext_quad_w).  With one rating per
+// lane the bf16 k = 112 block-fused kernel allocates 131 VGPRs instead of
+// 127 and drops from 4 waves per SIMD to 3; every other instantiation
+// keeps its occupancy.
+template <int KT, bool FP8, int NLANES = WAVE, bool WT = false,
+          bool IDENT = false, bool WIDEN = false, bool WIDE = false,
+          bool EXT8 = false>
+DEV_INLINE void stage_chunk_w(char* buf,
+                              const int* __restrict__ indices,
+                              const float* __restrict__ values,
+                              const void* __restrict__ factors_v,
+                              long long base, int nrem, int lane,
+                              const float* __restrict__ scale = nullptr) {
+    static_assert(NLANES >= 32, "the EXT rows take 32 lanes");
+    const bool full = WIDE && !IDENT && nrem >= 32;
+    [[maybe_unused]] float xr = 0.0f;
+    if constexpr (!IDENT && EXT8) {
+        static_assert(!WIDE, "EXT8 goes with the guarded gather");
+        if (lane < 8) stage_ext_quad_w<KT, FP8>(buf, values, base, nrem, lane);
+    } else if constexpr (!IDENT) {
+        if (lane < 32) {
+            xr = stage_ext_load(values, base, nrem, lane, full);
+            if constexpr (!WIDE) stage_ext_commit<KT, FP8>(buf, lane, xr);
+        }
+    }
+    stage_gather_w<KT, FP8, NLANES, WT, IDENT, WIDEN>(
+        buf, indices, factors_v, base, nrem, lane, 0, full, scale);
+    if constexpr (!IDENT && WIDE) {
+        if (lane < 32) stage_ext_commit<KT, FP8>(buf, lane, xr);
+    }
+}
+
+// Zero the never-restaged EXT pad rows K+2..K+15 of one stage buffer with
+// 16-byte stores: the 14 rows are one contiguous, 16-byte-aligned range
+// ((K+2)*TROW and TROW*14 are multiples of 16 for both row strides; the
+// rows' own pad bytes inside it are never read).  ``i`` / ``stride``: this
+// thread's index and the thread count.
+template <int KT, bool FP8>
+DEV_INLINE void stage_zero_pad(char* buf, int i, int stride) {
+    constexpr int K = Geo<KT>::K;
+    constexpr int TROW = FP8 ? Geo<KT>::TROW8 : Geo<KT>::TROW;
+    constexpr int N16 = 14 * TROW / 16;
+    static_assert((14 * TROW) % 16 == 0 && ((K + 2) * TROW) % 16 == 0,
+                  "pad rows must be a 16-byte-aligned range");
+    char* pad = buf + (long long)(K + 2) * TROW;
+    for (; i < N16; i += stride)
+        *(uint4*)(pad + (long long)i * 16) = uint4{0u, 0u, 0u, 0u};
+}
+
+// ... of all NCH stage buffers once per entity (block-wide).
 template <int KT, bool FP8, int NCH>
 DEV_INLINE void stage_zero_pad_all(char* smem) {
     constexpr int K = Geo<KT>::K;
     constexpr int TROW = FP8 ? Geo<KT>::TROW8 : Geo<KT>::TROW;
     constexpr int SB = (K + 16) * TROW;
-    constexpr int SEGS = FP8 ? 8 : 16;   // live u32 segments per row
-    for (int i = threadIdx.x; i < NCH * 14 * SEGS; i += 256) {
-        const int b = i / (14 * SEGS), rem = i % (14 * SEGS);
-        const int row = K + 2 + rem / SEGS, seg = rem % SEGS;
-        *(unsigned*)(smem + (long long)b * SB + (long long)row * TROW
-                     + seg * 4) = 0u;
-    }
+#pragma unroll
+    for (int b = 0; b < NCH; ++b)
+        stage_zero_pad<KT, FP8>(smem + (long long)b * SB, threadIdx.x, 256);
 }
 
 // ------------------------------------------------------------- frag reads
@@ -655,7 +812,8 @@ DEV_INLINE int gramian_to_lds(char* smem,
     const int nchunks = (n + 31) >> 5;
     for (int r0 = 0; r0 < nchunks; r0 += NCHU) {
         if (team < NCHU && r0 + team < nchunks)
-            stage_chunk_w<KT, FP8, TW * WAVE, WT>(
+            stage_chunk_w<KT, FP8, TW * WAVE, WT, false, false, false,
+                          /*EXT8=*/(!FP8 && KT == 7)>(
                 smem + team * SB, indices, values, factors,
                 p0 + (long long)(r0 + team) * 32, n - (r0 + team) * 32,
                 tlane, scale);

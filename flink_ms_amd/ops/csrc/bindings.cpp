@@ -873,6 +873,21 @@ void dbg_stage_dump(torch::Tensor indptr, torch::Tensor indices,
               a.name());
 }
 
+// The same through the e4m3 stage: byte factors, [k+16][32]-byte image.
+void dbg_stage_dump_fp8(torch::Tensor indptr, torch::Tensor indices,
+                        torch::Tensor values, torch::Tensor factors,
+                        torch::Tensor out, int64_t stream) {
+    Args a("dbg_stage_dump_fp8");
+    TORCH_CHECK(a.csr(indptr, indices, values) >= 1, a.name(),
+                ": indptr must hold at least one entity");
+    const int k = a.factors(factors, /*fp8=*/true, "factors");
+    a.flat(out, kU8, "out", (int64_t)(k + 16) * 32, /*exact=*/false);
+    check_hip(fma_dbg_stage_dump_fp8(k, i64(indptr), i32(indices),
+                                     f32(values), u8(factors), u8(out),
+                                     a.stream(stream)),
+              a.name());
+}
+
 // ``out`` holds [4 waves][k/16 + 1 tiles][64 lanes][8] fragment elements.
 void dbg_frag_dump(torch::Tensor indptr, torch::Tensor indices,
                    torch::Tensor values, torch::Tensor factors,
@@ -953,6 +968,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("stream"));
     m.def("rank_chunk_items", &rank_chunk_items);
     m.def("dbg_stage_dump", &dbg_stage_dump);
+    m.def("dbg_stage_dump_fp8", &dbg_stage_dump_fp8);
     m.def("dbg_frag_dump", &dbg_frag_dump);
     m.def("dbg_gramian", &dbg_gramian);
     m.def("mfma_probe_f32", &mfma_probe_f32);

@@ -8,28 +8,36 @@
 #include "als_kernels_device.inc"
 #include "fma_api.h"
 
-// Dump the staged Gt LDS image (one chunk): out[(K+16)][32] bf16.
-template <int KT>
+// Dump the staged Gt LDS image (one chunk): out[(K+16)][32] bf16 words or
+// e4m3 bytes.  The buffer starts out as 0xA5 bytes, so every element the
+// staging (pad-row zeroing included) fails to write shows in the image.
+template <int KT, bool FP8>
 __launch_bounds__(256)
 __global__ void k_stage_dump(const long long* __restrict__ indptr,
                              const int* __restrict__ indices,
                              const float* __restrict__ values,
-                             const unsigned short* __restrict__ factors,
-                             unsigned short* __restrict__ out) {
+                             const typename GatherT<FP8>::elem* __restrict__
+                                 factors,
+                             typename GatherT<FP8>::elem* __restrict__ out) {
+    using elem = typename GatherT<FP8>::elem;
     constexpr int K = Geo<KT>::K;
-    constexpr int TROW = Geo<KT>::TROW;
-    __shared__ __align__(16) char smem[Geo<KT>::SMEM];
+    constexpr int TROW = FP8 ? Geo<KT>::TROW8 : Geo<KT>::TROW;
+    constexpr int SB = (K + 16) * TROW;
+    __shared__ __align__(16) char smem[SB];
     const long long p0 = indptr[0];
     const int n = (int)(indptr[1] - p0);
-    stage_zero_pad_all<KT, false, 1>(smem);
-    if (threadIdx.x < 64)
-        stage_chunk_w<KT, false>(smem, indices, values, factors, p0, n,
-                                 threadIdx.x);
+    for (int i = threadIdx.x; i < SB / 4; i += 256)
+        ((unsigned*)smem)[i] = 0xA5A5A5A5u;
+    __syncthreads();
+    stage_zero_pad_all<KT, FP8, 1>(smem);
+    if (threadIdx.x < 64)   // WIDE: a full chunk takes the unguarded path
+        stage_chunk_w<KT, FP8, WAVE, false, false, false, true>(
+            smem, indices, values, factors, p0, n, threadIdx.x);
     __syncthreads();
     for (int i = threadIdx.x; i < (K + 16) * 32; i += 256) {
         const int row = i / 32, col = i % 32;
-        out[i] = *(const unsigned short*)(smem + (long long)row * TROW
-                                          + col * 2);
+        out[i] = *(const elem*)(smem + (long long)row * TROW
+                                + col * sizeof(elem));
     }
 }
 
@@ -95,7 +103,20 @@ extern "C" int fma_dbg_stage_dump(
     const unsigned short* factors, unsigned short* out, void* stream) {
     if (k % 16) return hipErrorInvalidValue;
     return dispatch_ic<1, 2, 3, 4, 5, 6, 7, 8>(k / 16, [&](auto kt) {
-        k_stage_dump<decltype(kt)::value>
+        k_stage_dump<decltype(kt)::value, false>
+            <<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>(
+                indptr, indices, values, factors, out);
+        return hipGetLastError();
+    });
+}
+
+// the e4m3 twin: factors and image are bytes
+extern "C" int fma_dbg_stage_dump_fp8(
+    int k, const long long* indptr, const int* indices, const float* values,
+    const unsigned char* factors, unsigned char* out, void* stream) {
+    if (k % 16) return hipErrorInvalidValue;
+    return dispatch_ic<1, 2, 3, 4, 5, 6, 7, 8>(k / 16, [&](auto kt) {
+        k_stage_dump<decltype(kt)::value, true>
             <<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>(
                 indptr, indices, values, factors, out);
         return hipGetLastError();

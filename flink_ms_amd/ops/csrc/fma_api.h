@@ -120,6 +120,9 @@ int fma_mfma_probe_fp8(const unsigned char* Xt /*[32][16]*/,
 int fma_dbg_stage_dump(int k, const long long* indptr, const int* indices,
                        const float* values, const unsigned short* factors,
                        unsigned short* out /*[k+16][32]*/, void* stream);
+int fma_dbg_stage_dump_fp8(int k, const long long* indptr, const int* indices,
+                           const float* values, const unsigned char* factors,
+                           unsigned char* out /*[k+16][32]*/, void* stream);
 int fma_dbg_frag_dump(int k, const long long* indptr, const int* indices,
                       const float* values, const unsigned short* factors,
                       unsigned short* out /*[4][k/16+1][64][8]*/,
