@@ -69,8 +69,14 @@ def _empty(device) -> torch.Tensor:
 def quantize_fp8(t: torch.Tensor) -> torch.Tensor:
     """fp32/bf16 -> OCP e4m3fn bytes (uint8).  The byte image is what the
     fp8 Gramian kernels gather (one cache line per k<=64 factor row) and
-    what the factor exchange ships over xGMI (half the bf16 bytes)."""
-    return t.to(torch.float8_e4m3fn).view(torch.uint8)
+    what the factor exchange ships over xGMI (half the bf16 bytes).
+
+    The contract of the kernels' ``f2fp8``, on the host too: round to
+    nearest, ties to the even byte; finite values beyond +-448 saturate to
+    +-448; inf and NaN become a NaN byte.  (A plain torch cast turns
+    everything above 464 into NaN, which would poison every entity that
+    gathers the value.)"""
+    return reference.quantize_fp8(t)
 
 
 def dequantize_fp8(t: torch.Tensor) -> torch.Tensor:
@@ -82,10 +88,11 @@ def fp8_rating_pair(r: torch.Tensor) -> torch.Tensor:
     """The EXT-column rating representation of the fp8 Gramian: e4m3 hi/lo
     pair with r ~= hi + lo (max relative error ~1.9e-3, see
     benchmarks/fp8_convergence_study.py).  Returns the dequantized
-    effective rating, for CPU references that must match the kernel."""
-    hi = dequantize_fp8(quantize_fp8(r.float()))
-    lo = dequantize_fp8(quantize_fp8(r.float() - hi))
-    return hi + lo
+    effective rating, for CPU references that must match the kernel: both
+    halves go through :func:`quantize_fp8`, so a finite rating beyond the
+    e4m3 range saturates (hi = +-448, lo = the saturated rest) exactly as
+    the kernels' staging does; inf and NaN give NaN."""
+    return reference.rating_pair(r, "fp8")
 
 
 def bf16_rating_pair(r: torch.Tensor) -> torch.Tensor:

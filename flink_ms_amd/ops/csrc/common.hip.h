@@ -16,9 +16,15 @@ typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef long long fp8x8;
 
-// float <-> OCP e4m3fn scalar conversions (round-to-nearest-even, matching
-// torch.float8_e4m3fn casts; conversions sit in staging/epilogue, not the
-// MFMA hot loop).
+// float <-> OCP e4m3fn scalar conversions; they sit in staging/epilogue, not
+// the MFMA hot loop.  The encode contract, shared by every e4m3 encoder of
+// the project (stage_rescale_fp8x4 here, ops.quantize_fp8 on the host):
+// round to nearest, ties to the even byte; finite values beyond +-448
+// SATURATE to +-448 (0x7E / 0xFE); inf and NaN become a NaN byte.  That is
+// a torch.float8_e4m3fn cast inside the range only: above 464 a plain torch
+// cast gives NaN, so the host clamps before it casts.  The decode is exact
+// (subnormals included).  tests/test_gpu_conversions.py holds every copy to
+// this over the whole value range.
 DEV_INLINE unsigned char f2fp8(float f) {
     __hip_fp8_e4m3 q(f);
     return q.__x;

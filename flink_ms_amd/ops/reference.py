@@ -101,9 +101,22 @@ def als_solve_side_reference(
 # ``gather`` names D: 'fp8' (e4m3), 'bf16', or None (fp32 tables: nothing is
 # rounded and pair_D is the identity).
 
+E4M3_MAX = 448.0
+
+
+def quantize_fp8(t: torch.Tensor) -> torch.Tensor:
+    """fp32/bf16 -> OCP e4m3fn bytes (uint8) under the one contract of every
+    e4m3 encoder of the project, the kernels' ``f2fp8`` included: round to
+    nearest, ties to the even byte; finite values beyond +-448 SATURATE to
+    +-448 (0x7E / 0xFE); inf and NaN become a NaN byte.  A plain torch cast
+    differs above the range: it makes everything past 464 a NaN."""
+    t = torch.where(torch.isfinite(t), t.clamp(-E4M3_MAX, E4M3_MAX), t)
+    return t.to(torch.float8_e4m3fn).view(torch.uint8)
+
+
 def _round_gather(t: torch.Tensor, gather: Optional[str]) -> torch.Tensor:
     if gather == "fp8":
-        return t.to(torch.float8_e4m3fn).to(torch.float32)
+        return quantize_fp8(t).view(torch.float8_e4m3fn).to(torch.float32)
     if gather == "bf16":
         return t.to(torch.bfloat16).to(torch.float32)
     if gather is None:
