@@ -170,6 +170,7 @@ class ALSTrainer:
             nc = max(1, self.cfg.exchange_chunks)
             self.item_chunked = ChunkedAllgather(ctx, self.ipart, nc)
             self.user_chunked = ChunkedAllgather(ctx, self.upart, nc)
+            global_ids = (self.user_csr.indices, self.item_csr.indices)
             self.user_csr.indices = self.item_chunked.remap_indices(
                 self.user_csr.indices).to(dev)
             self.item_csr.indices = self.user_chunked.remap_indices(
@@ -211,6 +212,8 @@ class ALSTrainer:
                 log.exception("overlapped-exchange setup failed; falling "
                               "back to the serial exchange")
                 self._overlap = False
+                # the serial exchange gathers rows in global id order
+                self.user_csr.indices, self.item_csr.indices = global_ids
         log.info(
             "ALS setup: %d users x %d items, %d local ratings, k=%d, "
             "world=%d, exchange=%s",

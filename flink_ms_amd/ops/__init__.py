@@ -225,8 +225,9 @@ def als_solve_side(
       ablation, ``FMA_WREG_BROADCAST=shfl`` the LDS-shuffle broadcasts.
     - k > 64 (or ``fused=True``): the block-fused kernel (triangular LDS
       A image, 4 blocks/CU).
-    - ``slab_rows``: the modular gramian -> batched-solve path, kept for
-      parity tests and A-materializing consumers.
+    - ``slab_rows`` (k <= 64; ignored above, where the block-fused kernel
+      runs): the modular gramian -> batched-solve path, kept for parity
+      tests and A-materializing consumers.
     ``other_factors`` dtype selects the gather precision: uint8 = e4m3
     bytes (one cache line per k<=64 row — the flagship path), anything
     else is cast to bf16.
@@ -299,15 +300,9 @@ def als_solve_side(
                                 _stream())
                 obs = ob[s:e] if ob.numel() > 0 else ob
                 o8s = o8[s:e] if o8.numel() > 0 else o8
-                if k <= 64:
-                    ops.ldl_solve_wave_reg(As, bs, out[s:e], obs, o8s,
-                                           _stream(), _wreg_broadcast())
-                else:
-                    ops.cholesky_solve(As, bs, out[s:e], _stream())
-                    if out_bf16 is not None:
-                        out_bf16[s:e].copy_(out[s:e].to(torch.bfloat16))
-                    if out_fp8 is not None:
-                        out_fp8[s:e].copy_(quantize_fp8(out[s:e]))
+                # k <= 64 here: larger ranks took the block-fused kernel
+                ops.ldl_solve_wave_reg(As, bs, out[s:e], obs, o8s,
+                                       _stream(), _wreg_broadcast())
         return out[:, :korig] if korig != k else out
     if w is not None:                        # CPU: the weighted reference
         out = reference.als_solve_weighted_reference(
@@ -344,9 +339,13 @@ def als_solve_chunk(
     argument).  This is the building block of the overlapped C1 exchange:
     the trainer solves slab i while slab i-1's factors are already in
     flight over xGMI (SURVEY.md §7 hard part).  ``scale`` / ``ext`` /
-    ``base``: the weighted solve, as in :func:`als_solve_side`."""
+    ``base``: the weighted solve, as in :func:`als_solve_side`.  An empty
+    ``entity_ids`` leaves the buffers alone (the launchers refuse
+    nrows = 0)."""
     w = _weights(scale, ext, base, csr.indices.numel(),
                  other_factors.shape[1])
+    if entity_ids.numel() == 0:
+        return
     if other_factors.is_cuda:
         ops = _require_hip()
         fp8 = other_factors.dtype == torch.uint8
@@ -365,8 +364,8 @@ def als_solve_chunk(
                       block=False, w=w)
         return
     # CPU (gloo tests): contiguous id range sliced out of the CSR
-    a = int(entity_ids.min()) if entity_ids.numel() else 0
-    b = int(entity_ids.max()) + 1 if entity_ids.numel() else 0
+    a = int(entity_ids.min())
+    b = int(entity_ids.max()) + 1
     nnz0, nnz1 = int(csr.indptr[a]), int(csr.indptr[b])
     sub = CSR(csr.indptr[a:b + 1] - nnz0, csr.indices[nnz0:nnz1],
               csr.values[nnz0:nnz1], b - a, csr.num_cols)

@@ -86,8 +86,10 @@ class ChunkedAllgather:
     """Overlap-friendly C1 factor exchange (SURVEY.md §7 hard part:
     "compute block i while exchanging block i+1").
 
-    The shard is split into ``chunks`` row slabs and the gathered replica
-    is laid out ``[slab][rank][slab_rows][k]`` so each slab's exchange is
+    The shard is split into at most ``chunks`` row slabs of one size, the
+    last possibly shorter and none empty (``.chunks`` is the count in use),
+    and the gathered replica is laid out ``[slab][rank][slab_rows][k]`` so
+    each slab's exchange is
     ONE contiguous ``all_gather_into_tensor`` — launchable on a side
     stream the moment the solver finishes writing that slab, while the
     solver's next slab is still running.  Consumers address the replica
@@ -100,6 +102,11 @@ class ChunkedAllgather:
         ss = part.shard_size
         self.chunks = max(1, min(chunks, ss))
         self.slab = (ss + self.chunks - 1) // self.chunks
+        # as many slabs as that slab size needs: rounding the slab up can
+        # cover the shard early (71 rows in 50 chunks = 36 slabs of 2), and
+        # a slab starting past the end would count negative rows
+        if self.slab:
+            self.chunks = (ss + self.slab - 1) // self.slab
         self.bounds = [(c * self.slab, min((c + 1) * self.slab, ss))
                        for c in range(self.chunks)]
         self.rows = [b - a for a, b in self.bounds]

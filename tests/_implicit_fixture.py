@@ -10,6 +10,12 @@ import torch
 from flink_ms_amd import ops
 from flink_ms_amd.data.blocked import CSR, csr_from_coo
 
+# Worst measured ratio of the EXPLICIT e4m3 kernel's distance from the
+# float64 oracle to the fp32 reference's, per fused path (the measurements
+# are in test_gpu_implicit.py's docstring).  e4m3 solves are allowed twice
+# this in place of the bf16 factor 4; shared with test_gpu_trainer_parity.py.
+FP8_EXPLICIT_RATIO = {"wave": 154.2, "block": 38.3}
+
 # chunk (32) and dual-chunk (64) edges of the staging loops
 ROW_LENGTHS = (0, 1, 2, 31, 32, 33, 63, 64, 65, 97, 129)
 

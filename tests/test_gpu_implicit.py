@@ -52,7 +52,7 @@ NCOLS = 50
 GATHERS = ["fp8", "bf16"]
 # worst measured ratio of the EXPLICIT e4m3 kernel to the fp32 reference's
 # distance from the oracle (module docstring); bf16 keeps the plain 4x
-FP8_EXPLICIT_RATIO = {"wave": 154.2, "block": 38.3}
+FP8_EXPLICIT_RATIO = fx.FP8_EXPLICIT_RATIO
 
 
 def _factor(gather, path):

@@ -253,5 +253,9 @@ def test_overlap_force_single_process():
         tr.fit()
         m = tr.model()
         out[mode] = (m.user_factors, m.item_factors)
-    assert (out["off"][0] - out["force"][0]).abs().max() < 1e-4
-    assert (out["off"][1] - out["force"][1]).abs().max() < 1e-4
+    # chunking changes when a row is solved, never an operand: same bits
+    # (tests/test_trainer_parity_cpu.py holds every mode to the replay)
+    assert T.equal(out["off"][0].view(T.int32),
+                   out["force"][0].view(T.int32))
+    assert T.equal(out["off"][1].view(T.int32),
+                   out["force"][1].view(T.int32))
