@@ -12,6 +12,7 @@ Reference job -> command (``python -m flink_ms_amd.cli.<name> --flags``):
   ALS/SVMKafkaConsumer     -> serve           (the serving job)
   ALSPredict.java          -> als_predict     (interactive)
   (no reference analog)    -> als_recommend   (interactive top-N)
+  (no reference analog)    -> als_foldin      (interactive new-user fold-in)
   SVMPredict.java          -> svm_predict     (interactive)
   ALSPredictRandom.java    -> als_predict_random
   SVMPredictRandom.java    -> svm_predict_random

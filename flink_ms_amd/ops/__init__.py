@@ -418,8 +418,20 @@ def gramian(csr: CSR, factors: torch.Tensor, reg: float, *,
     return reference.gramian_reference(csr, factors, reg)
 
 
+def _gram_rows(rows: torch.Tensor, ntable: int) -> torch.Tensor:
+    """Validate a ``factor_gram`` row list against a table of ``ntable``
+    rows: 1-D int64 / int32, every entry a row of the table."""
+    if rows.dim() != 1 or rows.dtype not in (torch.int64, torch.int32):
+        raise ValueError("rows must be a 1-D int64 or int32 tensor")
+    if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= ntable):
+        raise ValueError(f"rows entries must be rows of factors "
+                         f"(0..{ntable - 1})")
+    return rows
+
+
 def factor_gram(factors: torch.Tensor,
-                rows_per_part: Optional[int] = None) -> torch.Tensor:
+                rows_per_part: Optional[int] = None, *,
+                rows: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``G = F^T F`` [k][k] fp32 over every row of a factor table: the base
     matrix of the implicit-feedback solves.  On the GPU the table is read
     as stored (uint8 = e4m3 bytes, else bf16; e4m3 is widened exactly to
@@ -427,9 +439,24 @@ def factor_gram(factors: torch.Tensor,
     the launcher's choice, see :func:`factor_gram_rows_per_part`) are added
     in a fixed order, so the result is bit-reproducible and exactly
     symmetric; it depends on ``rows_per_part`` only within fp32 rounding.
-    Ranks up to 128."""
+    Ranks up to 128.
+
+    ``rows`` (int64 or int32, 1-D): sum over these rows of the table only,
+    ``G = sum_j F[rows[j]] F[rows[j]]^T`` -- the live rows of a serving
+    table, read in place (no compacted copy).  Rows may repeat (a repeated
+    row counts once per occurrence) and come in any order; every entry must
+    be a row of the table, which is checked here (the kernel does not).
+    Parts are over list positions, so with the same ``rows_per_part`` the
+    GPU result is bit-equal to ``factor_gram(F[rows])``: the same MFMA
+    sequence, hence as reproducible and exactly symmetric.  An empty list
+    gives zeros.  The GPU path takes tables of fewer than 2^31 rows.  A
+    table whose rank is not a multiple of 16 (or that is not stored as
+    bf16 / e4m3) pays one padded (converted) copy of the whole table per
+    call."""
     if factors.dim() != 2:
         raise ValueError("factors must be 2-D")
+    if rows is not None:
+        rows = _gram_rows(rows, factors.shape[0])
     if factors.is_cuda:
         ops = _require_hip()
         fp8 = factors.dtype == torch.uint8
@@ -442,12 +469,23 @@ def factor_gram(factors: torch.Tensor,
         k, korig = fac.shape[1], factors.shape[1]
         if k > 128:
             raise ValueError(f"factor_gram handles rank <= 128, got {korig}")
+        if rows is not None:
+            if fac.shape[0] >= 2 ** 31:
+                raise ValueError("factor_gram(rows=) handles tables of fewer "
+                                 f"than 2^31 rows, got {fac.shape[0]}")
+            if rows.numel() == 0:
+                return torch.zeros(korig, korig, dtype=torch.float32,
+                                   device=fac.device)
+            G = ops.factor_gram_rows(
+                fac, rows.to(device=fac.device, dtype=torch.int32)
+                .contiguous(), int(rows_per_part or 0), _stream())
+            return G[:korig, :korig] if korig != k else G
         if fac.shape[0] == 0:
             return torch.zeros(korig, korig, dtype=torch.float32,
                                device=fac.device)
         G = ops.factor_gram(fac, int(rows_per_part or 0), _stream())
         return G[:korig, :korig] if korig != k else G
-    return reference.factor_gram_reference(factors)
+    return reference.factor_gram_reference(factors, rows)
 
 
 def factor_gram_rows_per_part(n: int, k: int) -> int:

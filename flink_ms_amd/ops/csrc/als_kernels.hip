@@ -1218,6 +1218,17 @@ __global__ void k_als_solve_wavefused(const long long* __restrict__ indptr,
 // 32 products with ~2^-17 relative precision (measured, docs/KERNELS.md),
 // short of the fp32 dot bound this matrix is held to -- it is added to
 // EVERY entity's normal equations.
+//
+// ROWS: G = sum_j F[rows[j]] F[rows[j]]^T over a row list (the live item
+// rows of a serving table).  n is the list length; parts, chunks and the
+// reduction run over list positions exactly as above, only the address of
+// a staged row changes (the guarded gather of stage_gather_w, no EXT rows).
+// Positions >= n stage as zeros and neither read rows[] nor load from the
+// table.  Rows may repeat (a repeated row counts once per occurrence) and
+// come in any order; every entry must be a row of the table -- the caller
+// checks, the kernel does not.  With the same rows_per_part the result is
+// bit-equal to the plain kernel on the compacted table F[rows]: it is the
+// same MFMA sequence, hence as reproducible and as symmetric.
 template <int KT, int t = 0>
 DEV_INLINE void factor_gram_store(const f32x4* T, float* dst, int g4, int li) {
     if constexpr (t < KT * (KT + 1) / 2) {
@@ -1231,10 +1242,11 @@ DEV_INLINE void factor_gram_store(const f32x4* T, float* dst, int g4, int li) {
     }
 }
 
-template <int KT, bool FP8>
+template <int KT, bool FP8, bool ROWS = false>
 __launch_bounds__(256)
 __global__ void k_factor_gram(
     const typename GatherT<FP8>::elem* __restrict__ factors,
+    const int* __restrict__ rows,  // ROWS: [n] table rows, else unused
     float* __restrict__ ws,      // [parts][K][K], lower tiles written
     long long n, long long rows_per_part, long long parts) {
     constexpr int K = KT * 16;
@@ -1255,9 +1267,13 @@ __global__ void k_factor_gram(
     const long long r0 = part * rows_per_part;
     const long long r1 = min(n, r0 + rows_per_part);
     for (long long base = r0; base < r1; base += 32) {
-        stage_chunk_w<KT, false, WAVE, false, true, FP8>(
-            buf, nullptr, nullptr, factors, base,
-            (int)min((long long)32, r1 - base), lane);
+        const int nrem = (int)min((long long)32, r1 - base);
+        if constexpr (ROWS)
+            stage_gather_w<KT, false, WAVE, false, false, FP8>(
+                buf, rows, factors, base, nrem, lane, 0, false);
+        else
+            stage_chunk_w<KT, false, WAVE, false, true, FP8>(
+                buf, nullptr, nullptr, factors, base, nrem, lane);
         WREG_FENCE();                  // cross-lane LDS write -> read
         bf16x8 frag[KT];
 #pragma unroll
@@ -1631,10 +1647,12 @@ extern "C" long long fma_factor_gram_workspace_bytes(long long n, int k,
     return (n + rpp - 1) / rpp * (long long)k * k * 4;
 }
 
-extern "C" int fma_factor_gram(int k, int fp8, const void* factors,
-                               long long n, long long rows_per_part,
-                               float* G, void* workspace,
-                               long long workspace_bytes, void* stream) {
+namespace {
+// rows == nullptr: the whole table, n rows; else the n-entry row list
+int factor_gram_launch(int k, int fp8, const void* factors, const int* rows,
+                       long long n, long long rows_per_part, float* G,
+                       void* workspace, long long workspace_bytes,
+                       void* stream) {
     const long long need = fma_factor_gram_workspace_bytes(n, k, rows_per_part);
     if (need < 0 || workspace_bytes < need || !workspace)
         return hipErrorInvalidValue;
@@ -1642,16 +1660,18 @@ extern "C" int fma_factor_gram(int k, int fp8, const void* factors,
     const long long parts = (n + rpp - 1) / rpp;
     return dispatch_ic<1, 2, 3, 4, 5, 6, 7, 8>(k / 16, [&](auto kt) {
         constexpr int KT = decltype(kt)::value;
-        if (fp8)
-            k_factor_gram<KT, true>
+        auto launch = [&](auto f8, auto rw) {
+            constexpr bool F8 = decltype(f8)::value;
+            constexpr bool RW = decltype(rw)::value;
+            k_factor_gram<KT, F8, RW>
                 <<<grid_wave(parts), kBlock, 0, (hipStream_t)stream>>>(
-                    (const unsigned char*)factors, (float*)workspace, n, rpp,
-                    parts);
-        else
-            k_factor_gram<KT, false>
-                <<<grid_wave(parts), kBlock, 0, (hipStream_t)stream>>>(
-                    (const unsigned short*)factors, (float*)workspace, n, rpp,
-                    parts);
+                    (const typename GatherT<F8>::elem*)factors, rows,
+                    (float*)workspace, n, rpp, parts);
+        };
+        using T = std::true_type;
+        using F = std::false_type;
+        if (rows) { if (fp8) launch(T{}, T{}); else launch(F{}, T{}); }
+        else      { if (fp8) launch(T{}, F{}); else launch(F{}, F{}); }
         hipError_t err = hipGetLastError();
         if (err != hipSuccess) return err;
         k_factor_gram_reduce<KT>
@@ -1659,6 +1679,26 @@ extern "C" int fma_factor_gram(int k, int fp8, const void* factors,
                 (const float*)workspace, G, parts);
         return hipGetLastError();
     });
+}
+}  // namespace
+
+extern "C" int fma_factor_gram(int k, int fp8, const void* factors,
+                               long long n, long long rows_per_part,
+                               float* G, void* workspace,
+                               long long workspace_bytes, void* stream) {
+    return factor_gram_launch(k, fp8, factors, nullptr, n, rows_per_part, G,
+                              workspace, workspace_bytes, stream);
+}
+
+extern "C" int fma_factor_gram_rows(int k, int fp8, const void* factors,
+                                    long long ntable, const int* rows,
+                                    long long nlist, long long rows_per_part,
+                                    float* G, void* workspace,
+                                    long long workspace_bytes, void* stream) {
+    if (!rows || ntable <= 0 || ntable > 0x7fffffffLL)
+        return hipErrorInvalidValue;
+    return factor_gram_launch(k, fp8, factors, rows, nlist, rows_per_part, G,
+                              workspace, workspace_bytes, stream);
 }
 
 extern "C" int fma_mfma_probe_f32(const float* A, const float* B, float* D,

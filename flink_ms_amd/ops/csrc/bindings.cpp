@@ -510,6 +510,45 @@ torch::Tensor factor_gram(torch::Tensor factors, int64_t rows_per_part,
     return G;
 }
 
+// G [k][k] = sum_j F[rows[j]] F[rows[j]]^T over an int32 row list of a
+// bf16 / e4m3 table F [n][k], k = 16..128.  Rows may repeat (counted once
+// per occurrence) and come in any order; every entry must be in [0, n) --
+// the Python wrapper checks, the kernel does not.  With the same
+// rows_per_part the result is bit-equal to factor_gram(F[rows]).
+torch::Tensor factor_gram_rows(torch::Tensor factors, torch::Tensor rows,
+                               int64_t rows_per_part, int64_t stream) {
+    Args a("factor_gram_rows");
+    const bool fp8 = factors.scalar_type() == kU8;
+    const int k = a.factors(factors, fp8, "factors");
+    const int64_t n = factors.size(0);
+    a.tensor(rows, kI32, "rows");
+    TORCH_CHECK(rows.dim() == 1, a.name(), ": rows must be 1-D, got ",
+                rows.sizes());
+    const int64_t nlist = rows.numel();
+    TORCH_CHECK(nlist >= 1, a.name(), ": rows must have at least one entry");
+    TORCH_CHECK(n >= 1 && n <= 0x7fffffffLL, a.name(),
+                ": factors must have 1..2^31-1 rows, got ", n);
+    TORCH_CHECK(k <= 128, a.name(), ": factors has rank ", k,
+                ", need at most 128");
+    TORCH_CHECK(rows_per_part >= 0, a.name(),
+                ": rows_per_part must be >= 0 (0 = the launcher's choice)");
+    void* st = a.stream(stream);   // device check, before any allocation
+    TORCH_CHECK(rows.device() == factors.device(), a.name(),
+                ": rows must be on the device of factors (", factors.device(),
+                "), got ", rows.device());
+    const long long ws_bytes =
+        fma_factor_gram_workspace_bytes(nlist, k, rows_per_part);
+    TORCH_CHECK(ws_bytes >= 0, a.name(), ": bad shape");
+    auto opts = factors.options().dtype(kF32);
+    auto ws = torch::empty({ws_bytes / 4}, opts);
+    auto G = torch::empty({k, k}, opts);
+    check_hip(fma_factor_gram_rows(k, fp8, factors.data_ptr(), n, i32(rows),
+                                   nlist, rows_per_part, f32(G),
+                                   ws.data_ptr(), ws_bytes, st),
+              a.name());
+    return G;
+}
+
 // Rows per part factor_gram uses for rows_per_part = 0; host-only.
 int64_t factor_gram_rows_per_part(int64_t n, int64_t k) {
     const long long r = fma_factor_gram_rows_per_part(n, (int)k);
@@ -946,6 +985,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("als_solve_wavefused_w", &als_solve_wavefused_w);
     m.def("factor_gram", &factor_gram, py::arg("factors"),
           py::arg("rows_per_part"), py::arg("stream"));
+    m.def("factor_gram_rows", &factor_gram_rows, py::arg("factors"),
+          py::arg("rows"), py::arg("rows_per_part"), py::arg("stream"));
     m.def("factor_gram_rows_per_part", &factor_gram_rows_per_part);
     m.def("cholesky_solve", &cholesky_solve);
     m.def("cholesky_solve_ph", &cholesky_solve_ph);

@@ -102,6 +102,16 @@ int fma_als_solve_wavefused_w(int k, int fp8, const long long* indptr,
 int fma_factor_gram(int k, int fp8, const void* factors, long long n,
                     long long rows_per_part, float* G, void* workspace,
                     long long workspace_bytes, void* stream);
+// The same over a row list: G = sum_j f[rows[j]] f[rows[j]]^T for the nlist
+// int32 entries of rows, each a row of the [ntable][k] table (not checked;
+// repeats count once per occurrence, any order).  Parts are over list
+// positions; the workspace is fma_factor_gram_workspace_bytes(nlist, k,
+// rows_per_part).  With the same rows_per_part, bit-equal to
+// fma_factor_gram on the compacted table.
+int fma_factor_gram_rows(int k, int fp8, const void* factors,
+                         long long ntable, const int* rows, long long nlist,
+                         long long rows_per_part, float* G, void* workspace,
+                         long long workspace_bytes, void* stream);
 long long fma_factor_gram_workspace_bytes(long long n, int k,
                                           long long rows_per_part);
 long long fma_factor_gram_rows_per_part(long long n, int k);

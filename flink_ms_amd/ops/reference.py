@@ -247,14 +247,23 @@ def als_solve_weighted_f64(csr: CSR, factors: torch.Tensor, reg: float,
     return _solve_nonempty(A, b, counts)
 
 
-def factor_gram_reference(factors: torch.Tensor) -> torch.Tensor:
-    """G = F^T F in fp32 over every row of the table."""
+def factor_gram_reference(factors: torch.Tensor,
+                          rows: Optional[torch.Tensor] = None
+                          ) -> torch.Tensor:
+    """G = F^T F in fp32 over every row of the table, or over the row list
+    ``rows`` (repeats count once per occurrence)."""
+    if rows is not None:
+        factors = factors[rows.long()]
     f = _table_f32(factors)
     return f.T @ f
 
 
-def factor_gram_f64(factors: torch.Tensor) -> torch.Tensor:
-    """Float64 oracle of the factor Gram matrix (table entries are exact)."""
+def factor_gram_f64(factors: torch.Tensor,
+                    rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Float64 oracle of the factor Gram matrix (table entries are exact),
+    over every row or over the row list ``rows``."""
+    if rows is not None:
+        factors = factors[rows.long()]
     f = _table_f32(factors).to(torch.float64)
     return f.T @ f
 

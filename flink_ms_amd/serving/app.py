@@ -13,6 +13,9 @@ server fronting the in-process stores:
   POST /als/recommend               top-n items per user (fused GPU top-k)
   POST /als/rank                    where an item ranks for a user (fused
                                     GPU score + rank count)
+  POST /als/foldin                  factor vectors (and top-n items) for NEW
+                                    users from their baskets; optionally
+                                    persisted as user rows
   POST /svm/predict                 SVMPredict / RangePartitionSVMPredict
   POST /sgd/update                  online SGD v1 step(s), SGD.java semantics
   POST /mse                         batch MSE over rating triples
@@ -36,6 +39,7 @@ from typing import List, Optional
 from fastapi import FastAPI, HTTPException
 from pydantic import BaseModel, Field
 
+from ..utils.textio import java_double_to_string
 from .store import ALSModelStore, SVMModelStore
 from .wal import IngestJournal, journal_dir
 
@@ -71,6 +75,22 @@ class RankBody(BaseModel):
     users: List[str]
     items: List[str]                            # one (user, item) per position
     exclude: Optional[List[List[str]]] = None   # item ids, one list per pair
+
+
+class FoldInBody(BaseModel):
+    items: List[List[str]]                      # one basket per new user
+    values: Optional[List[List[float]]] = None  # default 1.0 per entry
+    regularization: float                       # the training lambda
+    implicit: bool = False
+    alpha: float = 1.0
+    n: int = 0                                  # 0 = no recommendations
+    exclude_seen: bool = True
+    exclude: Optional[List[List[str]]] = None   # item ids, one list per basket
+    users: Optional[List[str]] = None           # present = persist as rows
+
+
+FOLDIN_MAX_BASKETS = 1024
+FOLDIN_MAX_ENTRIES = 65536
 
 
 class SGDBody(BaseModel):
@@ -372,6 +392,65 @@ def create_app(als_store: Optional[ALSModelStore] = None,
             exclude)
         return {"found": found, "greater": greater, "equal": equal,
                 "candidates": cands, "score": score}
+
+    @app.post("/als/foldin")
+    def als_foldin(body: FoldInBody):
+        """Fold NEW users in from their baskets: one ALS user half-iteration
+        against the item factors being served (fused Gramian + solve
+        kernels; no reference analog), then with ``n`` > 0 the top-n live
+        items per basket.  Ids are normalised as in /als/recommend; item
+        ids that resolve nowhere are ignored (``used`` counts the rest).
+        ``users`` persists every basket with ``used`` > 0 as a user row,
+        journaled and pushed to the kv plane like the SGD rows."""
+        nb = len(body.items)
+        if nb > FOLDIN_MAX_BASKETS:
+            raise HTTPException(
+                400, f"at most {FOLDIN_MAX_BASKETS} baskets per request")
+        if sum(len(b) for b in body.items) > FOLDIN_MAX_ENTRIES:
+            raise HTTPException(
+                400, f"at most {FOLDIN_MAX_ENTRIES} entries per request")
+        if body.values is not None and (
+                len(body.values) != nb
+                or any(len(v) != len(b)
+                       for v, b in zip(body.values, body.items))):
+            raise HTTPException(400, "items/values length mismatch")
+        if body.exclude is not None and len(body.exclude) != nb:
+            raise HTTPException(400, "items/exclude length mismatch")
+        if body.users is not None and len(body.users) != nb:
+            raise HTTPException(400, "items/users length mismatch")
+        if not 0 <= body.n <= 128:
+            raise HTTPException(400, "n must be in 0..128")
+        if body.regularization < 0:
+            raise HTTPException(400, "regularization must be >= 0")
+
+        def norm(s: str) -> str:
+            return s.strip().upper()
+
+        values = body.values or [[1.0] * len(b) for b in body.items]
+        baskets = [[(norm(i), float(v)) for i, v in zip(b, vals)]
+                   for b, vals in zip(body.items, values)]
+        users = None if body.users is None else [norm(u) for u in body.users]
+        kw = dict(implicit=body.implicit, alpha=body.alpha, user_ids=users)
+        try:
+            if body.n:
+                exclude = (None if body.exclude is None else
+                           [[norm(i) for i in ids] for ids in body.exclude])
+                used, X, items, scores, rows = als.fold_in_recommend(
+                    baskets, body.n, body.regularization,
+                    exclude_seen=body.exclude_seen, exclude=exclude, **kw)
+            else:
+                used, X, rows = als.fold_in(baskets, body.regularization,
+                                            **kw)
+                items = [[] for _ in baskets]
+                scores = [[] for _ in baskets]
+        except ValueError as e:   # duplicate item, reserved id, rank > 128
+            raise HTTPException(400, str(e))
+        _journal("als", rows)
+        _kv_push(rows)
+        return {"used": used,
+                "factors": [";".join(java_double_to_string(v) for v in x)
+                            for x in X.tolist()],
+                "items": items, "scores": scores, "rows": rows}
 
     @app.post("/svm/predict")
     def svm_predict(body: SVMPredictBody):

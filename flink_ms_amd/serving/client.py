@@ -61,6 +61,24 @@ class QueryClientHelper:
         r.raise_for_status()
         return r.json()
 
+    def als_fold_in(self, items: List[List[str]],
+                    values: Optional[List[List[float]]] = None,
+                    regularization: float = 0.1, **kw) -> dict:
+        """Fold new users in from their baskets (/als/foldin): ``items[i]``
+        is basket ``i``'s item ids, ``values[i]`` its ratings / strengths
+        (default 1.0 each), ``regularization`` the training lambda.
+        Keywords as in the endpoint's body: ``implicit``, ``alpha``, ``n``
+        (top-n items per basket, 0 = none), ``exclude_seen``, ``exclude``,
+        ``users`` (persist as user rows).  Returns ``{"used", "factors",
+        "items", "scores", "rows"}``, one entry per basket."""
+        payload: dict = {"items": items, "regularization": regularization}
+        if values is not None:
+            payload["values"] = values
+        payload.update(kw)
+        r = self._client.post(f"{self.base}/als/foldin", json=payload)
+        r.raise_for_status()
+        return r.json()
+
     def svm_predict(self, vector: str, output_decision_function: bool = False,
                     threshold_value: float = 0.0,
                     range_size: Optional[int] = None) -> dict:

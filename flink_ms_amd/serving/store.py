@@ -57,6 +57,8 @@ class FactorBlocks:
         self.texts: list = []                   # bytes or mmap objects
         self._overlay: Dict[Tuple[str, int], List[float]] = {}
         self.spilled: Dict[str, bool] = {"U": False, "I": False}
+        # device-value writes per kind (the store's item-Gram cache key)
+        self.writes: Dict[str, int] = {"U": 0, "I": 0}
 
     def _ensure(self, kind: str, add: int, k: int) -> None:
         if self.k is None:
@@ -107,6 +109,7 @@ class FactorBlocks:
         # ONE H2D slab (the r1 store copied row at a time)
         self.dev[kind][start:start + n] = (
             facs.to(self.device).to(torch.bfloat16))
+        self.writes[kind] += 1
         self.idmap[kind].update(zip(ids.tolist(), range(start, start + n)))
         if text is not None:
             bi = len(self.texts)
@@ -162,6 +165,7 @@ class FactorBlocks:
         else:
             self._overlay[(kind, r)] = list(vec)
         self.dev[kind][r] = t.to(self.device).to(torch.bfloat16)
+        self.writes[kind] += 1
         self.src[kind][r] = None
         return True
 
@@ -186,6 +190,9 @@ class ALSModelStore:
         # recommend(): candidate item rows per source, cached per version
         self._cand_version = 0     # bumped whenever a key gains a new row
         self._cand_cache: Optional[tuple] = None
+        # fold-in: Gram matrix of the live item rows, cached per version
+        self._item_version = 0     # bumped whenever an item row's device
+        self._gram_cache: Optional[tuple] = None   # values are written
 
     # ------------------------------------------------------------ ingest
 
@@ -255,6 +262,7 @@ class ALSModelStore:
                                        keep_host=False)
                 n += cnt
             self._cand_version += 1
+            self._item_version += 1
             if n and self._payload:
                 for kind_code, kind in ((0, "U"), (1, "I")):
                     sel = kinds == kind_code
@@ -280,6 +288,9 @@ class ALSModelStore:
             self._rows.clear()
             self._mirror_len = 0
             self._cand_version += 1
+            self._item_version += 1
+        if key.endswith("-I"):
+            self._item_version += 1
         row = self._rows.get(key)
         if row is None:
             self._cand_version += 1
@@ -321,6 +332,7 @@ class ALSModelStore:
             self._blocks.add_block("U", uid, uf)
             self._blocks.add_block("I", iid, itf)
             self._cand_version += 1
+            self._item_version += 1
             if self._k is None:
                 self._k = int(user_factors.shape[1])
 
@@ -374,6 +386,7 @@ class ALSModelStore:
                                        offs[sel], lens[sel])
                 n += cnt
             self._cand_version += 1
+            self._item_version += 1
             if n:
                 # bulk rows supersede earlier scalar payloads (last-writer
                 # wins) — drop only the stale overlapping entries
@@ -511,6 +524,88 @@ class ALSModelStore:
         self._cand_cache = cache
         return cache
 
+    def _exclusion_rows(self, lists: List[List[str]]
+                        ) -> Tuple[List[List[int]], List[List[int]]]:
+        """Per query the sorted (mirror rows, block rows) of the item ids in
+        ``lists`` (a mirror key shadows a block row; unknown ids are
+        ignored).  Caller holds ``_lock``."""
+        blocks = self._blocks
+        idmap = blocks.idmap["I"] if blocks is not None else {}
+        ex_m: List[List[int]] = []
+        ex_b: List[List[int]] = []
+        for ids in lists:
+            rm, rb = set(), set()
+            for item in ids:
+                row = self._rows.get(als_state_key(item, "I"))
+                if row is not None:
+                    rm.add(row)
+                    continue
+                try:
+                    row = idmap.get(int(item))
+                except ValueError:
+                    row = None
+                if row is not None:
+                    rb.add(row)
+            ex_m.append(sorted(rm))
+            ex_b.append(sorted(rb))
+        return ex_m, ex_b
+
+    def _top_items(self, Q: torch.Tensor, n: int,
+                   ex: Optional[Tuple[List[List[int]], List[List[int]]]],
+                   mirror: Optional[torch.Tensor],
+                   blocks: Optional[FactorBlocks], cands: tuple
+                   ) -> Tuple[List[List[str]], List[List[float]]]:
+        """Top-``n`` live items for every bf16 query row of ``Q``: one fused
+        score + top-k launch per item source, merged per query on the host
+        (score descending, then item id, numeric ids by value).  ``ex``:
+        per query the excluded rows per source (:meth:`_exclusion_rows`) or
+        ``None``; ``mirror`` / ``blocks`` / ``cands`` are the caller's
+        snapshot (``_item_candidates()[1:]``) taken under ``_lock``."""
+        from .. import ops
+        (m_cand, m_ids), (b_cand, b_ids) = cands
+        ex_m, ex_b = ex if ex is not None else (None, None)
+        nq = Q.shape[0]
+
+        def csr(lists: Optional[List[List[int]]]):
+            if lists is None:
+                return None
+            ptr = [0]
+            for rows in lists:
+                ptr.append(ptr[-1] + len(rows))
+            flat = [r for rows in lists for r in rows]
+            return (torch.tensor(ptr, dtype=torch.int64).to(self.device),
+                    torch.tensor(flat, dtype=torch.int64).to(self.device))
+
+        merged: List[List[Tuple[float, str]]] = [[] for _ in range(nq)]
+        for V, cand, ids, exl in (
+                (mirror, m_cand, m_ids, ex_m),
+                (blocks.dev["I"] if blocks is not None and "I" in blocks.dev
+                 else None, b_cand, b_ids, ex_b)):
+            if V is None or cand is None:
+                continue
+            s, r = ops.topk_scores(Q, V, n, cand=cand, exclude=csr(exl))
+            s, r = s.cpu().tolist(), r.cpu().tolist()
+            for j in range(nq):
+                merged[j].extend((sc, ids[row])
+                                 for sc, row in zip(s[j], r[j]) if row >= 0)
+
+        def order(entry: Tuple[float, str]):
+            sc, item = entry
+            try:
+                ident = (0, int(item), "")
+            except ValueError:
+                ident = (1, 0, item)
+            # NaN scores after every number, as in the kernel
+            return (1, 0.0, ident) if sc != sc else (0, -sc, ident)
+
+        items: List[List[str]] = []
+        scores: List[List[float]] = []
+        for j in range(nq):
+            best = sorted(merged[j], key=order)[:n]
+            items.append([item for _, item in best])
+            scores.append([float(sc) for sc, _ in best])
+        return items, scores
+
     def recommend(self, user_ids: List[str], n: int,
                   exclude: Optional[List[List[str]]] = None
                   ) -> Tuple[List[bool], List[List[str]], List[List[float]]]:
@@ -524,7 +619,6 @@ class ALSModelStore:
         not get (unknown ids are ignored).  Returns ``(found, items,
         scores)``; an unknown user has ``found`` False and empty lists, and
         a list is shorter than ``n`` when fewer items remain."""
-        from .. import ops
         n = int(n)
         if not 1 <= n <= 128:
             raise ValueError(f"n must be in 1..128, got {n}")
@@ -534,29 +628,12 @@ class ALSModelStore:
             um, ua = self._batch_rows(user_ids, "U")
             mirror = self._mirror
             blocks = self._blocks
-            _, (m_cand, m_ids), (b_cand, b_ids) = self._item_candidates()
+            cands = self._item_candidates()[1:]
             found_t = (um >= 0) | (ua >= 0)
             sel = found_t.nonzero(as_tuple=True)[0].tolist()
-            # exclusion ids -> sorted rows per source (mirror shadows blocks)
-            ex_m: List[List[int]] = []
-            ex_b: List[List[int]] = []
+            ex = None
             if exclude is not None:
-                idmap = blocks.idmap["I"] if blocks is not None else {}
-                for qi in sel:
-                    rm, rb = set(), set()
-                    for item in exclude[qi]:
-                        row = self._rows.get(als_state_key(item, "I"))
-                        if row is not None:
-                            rm.add(row)
-                            continue
-                        try:
-                            row = idmap.get(int(item))
-                        except ValueError:
-                            row = None
-                        if row is not None:
-                            rb.add(row)
-                    ex_m.append(sorted(rm))
-                    ex_b.append(sorted(rb))
+                ex = self._exclusion_rows([exclude[qi] for qi in sel])
         found = found_t.tolist()
         items: List[List[str]] = [[] for _ in user_ids]
         scores: List[List[float]] = [[] for _ in user_ids]
@@ -572,44 +649,201 @@ class ALSModelStore:
         if bool((~in_m).any()):
             Q[(~in_m).to(self.device)] = blocks.dev["U"][
                 ua[sel_t][~in_m].to(self.device)]
-
-        def csr(lists: List[List[int]]):
-            if exclude is None:
-                return None
-            ptr = [0]
-            for rows in lists:
-                ptr.append(ptr[-1] + len(rows))
-            flat = [r for rows in lists for r in rows]
-            return (torch.tensor(ptr, dtype=torch.int64).to(self.device),
-                    torch.tensor(flat, dtype=torch.int64).to(self.device))
-
-        merged: List[List[Tuple[float, str]]] = [[] for _ in sel]
-        for V, cand, ids, ex in (
-                (mirror, m_cand, m_ids, ex_m),
-                (blocks.dev["I"] if blocks is not None and "I" in blocks.dev
-                 else None, b_cand, b_ids, ex_b)):
-            if V is None or cand is None:
-                continue
-            s, r = ops.topk_scores(Q, V, n, cand=cand, exclude=csr(ex))
-            s, r = s.cpu().tolist(), r.cpu().tolist()
-            for j in range(len(sel)):
-                merged[j].extend((sc, ids[row])
-                                 for sc, row in zip(s[j], r[j]) if row >= 0)
-
-        def order(entry: Tuple[float, str]):
-            sc, item = entry
-            try:
-                ident = (0, int(item), "")
-            except ValueError:
-                ident = (1, 0, item)
-            # NaN scores after every number, as in the kernel
-            return (1, 0.0, ident) if sc != sc else (0, -sc, ident)
-
+        top_i, top_s = self._top_items(Q, n, ex, mirror, blocks, cands)
         for j, qi in enumerate(sel):
-            best = sorted(merged[j], key=order)[:n]
-            items[qi] = [item for _, item in best]
-            scores[qi] = [float(sc) for sc, _ in best]
+            items[qi], scores[qi] = top_i[j], top_s[j]
         return found, items, scores
+
+    # ------------------------------------------------------------ fold-in
+
+    def _item_gram(self) -> torch.Tensor:
+        """``G0 = sum v v^T`` [k][k] fp32 over every live item row: the base
+        matrix of an implicit fold-in.  ``factor_gram`` over the mirror's
+        live rows plus ``factor_gram`` over the blocks' live rows (added in
+        that order, in fp32), read in place through the row lists of
+        :meth:`_item_candidates`; a missing or empty source contributes
+        nothing.  Cached until an item row's device values are written
+        (``_item_version`` and the blocks' own write count)."""
+        from .. import ops
+        with self._lock:
+            blocks = self._blocks
+            key = (self._item_version,
+                   blocks.writes["I"] if blocks is not None else 0)
+            cache = self._gram_cache
+            if cache is not None and cache[0] == key:
+                return cache[1]
+            (m_cand, _), (b_cand, _) = self._item_candidates()[1:]
+            G = None
+            for V, cand in (
+                    (self._mirror, m_cand),
+                    (blocks.dev["I"] if blocks is not None
+                     and "I" in blocks.dev else None, b_cand)):
+                if V is None or cand is None:
+                    continue
+                part = ops.factor_gram(V, rows=cand)
+                G = part if G is None else G + part
+            if G is None:
+                k = self._k or 0
+                G = torch.zeros(k, k, dtype=torch.float32, device=self.device)
+            self._gram_cache = (key, G)
+            return G
+
+    def fold_in(self, baskets: List[List[Tuple[str, float]]], reg: float, *,
+                implicit: bool = False, alpha: float = 1.0,
+                user_ids: Optional[List[str]] = None
+                ) -> Tuple[List[int], torch.Tensor, List[str]]:
+        """Factor vectors for NEW users from their baskets: one ALS user
+        half-iteration against the item factors being served.  Each basket
+        is a list of ``(item_id, value)``; item ids resolve as everywhere
+        else (a mirror key shadows a block row), ids that resolve nowhere
+        are ignored and ``used[i]`` counts the resolved entries.  The same
+        item twice in one basket raises ``ValueError``.
+
+        Explicit models solve the ridge system ``(sum y y^T + reg*n I) x =
+        sum r y``; ``implicit=True`` solves the Hu-Koren-Volinsky system
+        ``(G0 + sum w y y^T + reg*n I) x = sum (1 + w) p y`` with ``w =
+        alpha*|r|``, ``p = [r > 0]`` and ``G0`` the Gram matrix of every
+        live item (:meth:`_item_gram`).  ``reg`` is the TRAINING lambda
+        (model files carry no metadata) and ``n = used[i]`` the trainer's
+        lambda*n convention: every resolved entry counts, zero and negative
+        implicit values included.  The resolved rows are gathered (bf16, in
+        basket order) into one compact table and solved by
+        ``ops.als_solve_side`` with its default dispatch (wave-fused kernel
+        up to rank 64, block-fused above, the references on CPU); rank
+        above 128 raises ``ValueError``.  As in the trainer, an implicit
+        row is re-rounded to bf16 after scaling by ``sqrt(alpha*|r|)``.
+
+        Returns ``(used, X, rows)``: ``X`` fp32 ``[len(baskets)][k]`` on the
+        CPU, a zero vector where ``used == 0``.  With ``user_ids`` (one id
+        per basket, ``MEAN`` refused) every basket with ``used > 0`` is
+        persisted as the row ``"<id>,U,<f;f;...>"`` through :meth:`ingest`
+        (last writer wins) and the emitted rows are returned for the
+        journal; otherwise ``rows`` is ``[]``."""
+        from .. import ops
+        from ..data.blocked import CSR
+        if user_ids is not None:
+            if len(user_ids) != len(baskets):
+                raise ValueError("user_ids must hold one id per basket")
+            for uid in user_ids:
+                if str(uid).strip().upper() == MEAN_ID:
+                    raise ValueError(f"user id {MEAN_ID} is reserved")
+        reg = float(reg)
+        dev = self.device
+        with self._lock:
+            k = self._k or 0
+            if k > 128:
+                raise ValueError(f"fold_in handles rank <= 128, got {k}")
+            mirror, blocks = self._mirror, self._blocks
+            idmap = blocks.idmap["I"] if blocks is not None else {}
+            used: List[int] = []
+            from_m: List[bool] = []
+            src_rows: List[int] = []
+            values: List[float] = []
+            for basket in baskets:
+                seen = set()
+                cnt = 0
+                for item, value in basket:
+                    row = self._rows.get(als_state_key(item, "I"))
+                    in_m = row is not None
+                    if not in_m:
+                        try:
+                            row = idmap.get(int(item))
+                        except ValueError:
+                            row = None
+                    ident = (in_m, row) if row is not None else str(item)
+                    if ident in seen:
+                        raise ValueError(
+                            f"item {item} appears twice in one basket")
+                    seen.add(ident)
+                    if row is None:
+                        continue
+                    from_m.append(in_m)
+                    src_rows.append(row)
+                    values.append(float(value))
+                    cnt += 1
+                used.append(cnt)
+            nnz = len(src_rows)
+            table = None
+            if nnz:
+                # one compact [nnz][k] bf16 table, basket order
+                table = torch.empty(nnz, k, dtype=torch.bfloat16, device=dev)
+                rows_t = torch.tensor(src_rows, dtype=torch.int64)
+                m_t = torch.tensor(from_m, dtype=torch.bool)
+                if bool(m_t.any()):
+                    table[m_t.to(dev)] = mirror[rows_t[m_t].to(dev)]
+                if bool((~m_t).any()):
+                    table[(~m_t).to(dev)] = blocks.dev["I"][
+                        rows_t[~m_t].to(dev)]
+            base = self._item_gram() if implicit and nnz else None
+        X = torch.zeros(len(baskets), k, dtype=torch.float32)
+        if nnz:
+            indptr = torch.zeros(len(baskets) + 1, dtype=torch.int64)
+            torch.cumsum(torch.tensor(used, dtype=torch.int64), 0,
+                         out=indptr[1:])
+            vals = torch.tensor(values, dtype=torch.float32).to(dev)
+            csr = CSR(indptr.to(dev),
+                      torch.arange(nnz, dtype=torch.int32, device=dev), vals,
+                      len(baskets), nnz)
+            if implicit:
+                s, e = ops.implicit_weights(vals, alpha)
+                X = ops.als_solve_side(csr, table, reg, scale=s, ext=e,
+                                       base=base)
+            else:
+                X = ops.als_solve_side(csr, table, reg)
+            X = X.to(torch.float32).cpu()
+        rows: List[str] = []
+        if user_ids is not None:
+            for uid, cnt, x in zip(user_ids, used, X.tolist()):
+                if cnt:
+                    rows.append(f"{uid},U," + ";".join(
+                        java_double_to_string(v) for v in x))
+            self.ingest(rows)
+        return used, X, rows
+
+    def fold_in_recommend(self, baskets: List[List[Tuple[str, float]]],
+                          n: int, reg: float, *, implicit: bool = False,
+                          alpha: float = 1.0, exclude_seen: bool = True,
+                          exclude: Optional[List[List[str]]] = None,
+                          user_ids: Optional[List[str]] = None
+                          ) -> Tuple[List[int], torch.Tensor,
+                                     List[List[str]], List[List[float]],
+                                     List[str]]:
+        """:meth:`fold_in`, then the top-``n`` live items for every new
+        user, with :meth:`recommend`'s ordering, merge and tie rules.  The
+        query is ``X.to(bfloat16)`` -- the value the mirror holds after
+        persisting, so a persisted user's later :meth:`recommend` returns
+        the same lists.  ``exclude_seen`` adds each basket's own items to
+        that user's exclusion; ``exclude[i]`` lists further ids.  Baskets
+        with ``used == 0`` get empty lists.  Returns ``(used, X, items,
+        scores, rows)``."""
+        n = int(n)
+        if not 1 <= n <= 128:
+            raise ValueError(f"n must be in 1..128, got {n}")
+        if exclude is not None and len(exclude) != len(baskets):
+            raise ValueError("exclude must hold one list per basket")
+        used, X, rows = self.fold_in(baskets, reg, implicit=implicit,
+                                     alpha=alpha, user_ids=user_ids)
+        items: List[List[str]] = [[] for _ in baskets]
+        scores: List[List[float]] = [[] for _ in baskets]
+        sel = [i for i, cnt in enumerate(used) if cnt]
+        if not sel:
+            return used, X, items, scores, rows
+        with self._lock:
+            mirror, blocks = self._mirror, self._blocks
+            cands = self._item_candidates()[1:]
+            ex = None
+            if exclude_seen or exclude is not None:
+                ex = self._exclusion_rows(
+                    [([str(item) for item, _ in baskets[i]]
+                      if exclude_seen else [])
+                     + (list(exclude[i]) if exclude is not None else [])
+                     for i in sel])
+        Q = X[torch.tensor(sel, dtype=torch.int64)].to(torch.bfloat16
+                                                       ).to(self.device)
+        top_i, top_s = self._top_items(Q, n, ex, mirror, blocks, cands)
+        for j, i in enumerate(sel):
+            items[i], scores[i] = top_i[j], top_s[j]
+        return used, X, items, scores, rows
 
     def rank(self, user_ids: List[str], item_ids: List[str],
              exclude: Optional[List[List[str]]] = None
@@ -807,6 +1041,8 @@ class ALSModelStore:
                 si = (im if isrc == "m" else ia)[sel].to(V.device)
                 ops.sgd_update(U, V, su, si, r_t[sel].to(U.device),
                                learning_rate, user_reg, item_reg)
+                with self._lock:       # V's item rows changed in place
+                    self._item_version += 1
                 batched += cnt
                 # coherence: batched read-back of the touched rows, then
                 # re-format payloads (reference emits updated rows back
